@@ -2,12 +2,22 @@
 """bench.py -- headline benchmark: hash group-by (sum, mean, count) of 1e9 int64-key rows x 1e6 keys (BASELINE.json
 configs[2], "group_by(int64 key).agg(sum,mean,count), 1e9 rows / 1e6 keys, 1 GPU"; configs[3] at N > 1).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one full pass of the hot path over the resident synthetic columns: pdx_groupby_create (keys -> first-occurrence
 group ids) + pdx_groupby_agg(sum, mean, count) (stable sort by group + Arrow-order pairwise reduce), inputs already in HBM,
-results left in HBM.  Rank 0 prints ONE JSON line:
+results left in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times K steps, writes the last step's outputs when --dump-outputs is given, and prints the line
+with `value`, `ms_per_step` and `roofline` (whose figures come from the timed steps themselves).  --full adds everything else,
+after the timed region: the result checks, `cpu_baseline`, `chain_check`, `secondary` / `general_keys_hash_path` and, for
+N > 1, the cross-check of the two sharded orchestrations; in a plain run those fields are null.
+
+  --dump-outputs DIR   the arrays the timed path returned in its last step, as float64 DIR/<name>.npy: group_keys, sum, mean,
+                       count (one entry per group, in the result's group order; the inputs are counter-based, so the same
+                       arguments give the same inputs on every run).  Above DUMP_BYTES in all, a fixed seeded sample of the
+                       groups is written instead, with its group positions in sample_index.npy.
 
   value / ms_per_step  whole-job rows per second of the timed region (barrier + synchronize on both sides, MAX over ranks)
   roofline             bound hbm; `achieved` / `frac` = ALGORITHMIC bytes of the step (16 B/row x local rows) / step time
@@ -45,13 +55,19 @@ OWN_BYTES_PER_ROW = {"radix_scatter": 20.5,   # narrowing passes: (4 + 8 -> 2 + 
                      "dense_slots": 12.0,     # 8 B key read, 4 B slot written
                      "fused_last_digit_reduce": 9.0,  # 1 B key + 8 B value read once
                      "seg_reduce": 8.0, "hash_probe_lds": 12.0, "radix_hist": 2.0}
+DUMP_BYTES = 64_000_000    # --dump-outputs: at most this many bytes of array data in all
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the result checks, cpu_baseline, chain_check, the secondary configs and (N > 1) "
+                         "the orchestration cross-check; a plain run only times the headline step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned in its last step to DIR/<name>.npy (float64)")
     ap.add_argument("--rows", type=float, default=1e9, help="total rows (strong scaling: split by row range over the ranks)")
     ap.add_argument("--keys", type=float, default=1e6)
     ap.add_argument("--cpu-sample-rows", type=float, default=1e8,
@@ -60,10 +76,31 @@ def parse_args():
     ap.add_argument("--chain-check-rows", type=float, default=1.35e8,
                     help="rows of the same workload pushed through the HIP path and the oracle after the timed region: enough for the default "
                          "thresholds to pick the SAME kernel chain as the timed step (narrowing sort + fused last digit need >= 8192 rows per run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other configs / the general-keys run after the timed region")
-    ap.add_argument("--no-check", action="store_true", help="skip the size-independent result checks after the timed region")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline and chain_check")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the other configs / the general-keys run after the timed region")
+    ap.add_argument("--no-check", action="store_true", help="(--full) skip the size-independent result checks after the timed region")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: 1-D array, one entry per group} -> out_dir/<name>.npy as float64 (the keys and row counts of this
+    workload are integers below 2^53, exact in float64).  Above DUMP_BYTES in all, the same seeded sample of group positions
+    for every array, written beside them as sample_index.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    G = len(next(iter(arrays.values())))
+    per_group = 8 * len(arrays)
+    if G * per_group > DUMP_BYTES:
+        k = DUMP_BYTES // (per_group + 8)
+        idx = np.sort(np.random.default_rng(20240611).choice(G, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["sample_index"] = idx
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def source_hash():
@@ -545,9 +582,20 @@ def main():
         elif not sharded:
             roof["traffic_note"] = "no counter traffic under profiles/ for this configuration, plan (slots=%s) and build: dropped" % slots
 
+    # what the last timed step returned (the sharded result is the whole job's, on every rank: rank 0 writes it)
+    if args.dump_outputs and rank == 0:
+        if not sharded:
+            gb, outs = res
+            arrays = {"group_keys": gb.unique_keys().to_numpy()[0]}
+            arrays.update((name, o.to_numpy()[0]) for name, o in zip(("sum", "mean", "count"), outs))
+        else:
+            arrays = {"group_keys": res["keys"].cpu().numpy()}
+            arrays.update((name, o[0].cpu().numpy()) for name, o in zip(("sum", "mean", "count"), res["outs"]))
+        dump_outputs(args.dump_outputs, arrays)
+
     # size-independent checks on the last result (outside the timed region)
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         if not sharded:
             gb, outs = res
             G = gb.num_groups
@@ -586,12 +634,12 @@ def main():
     res = None
 
     secondary = None
-    if rank == 0 and not sharded and not args.no_secondary:
+    if args.full and rank == 0 and not sharded and not args.no_secondary:
         lib.pdx_trim_pool()
         secondary = secondary_runs(torch, L, K, api, keys, vals, kinds, n_total, nkeys, args.steps)
 
     cpu = None
-    if rank == 0 and not sharded and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not sharded and not args.no_cpu_baseline:
         def gpu_on_sample(m):
             gb = K.GroupByHandle.create(keys.slice(0, m))
             o = gb.agg(vals.slice(0, m), kinds)
@@ -604,7 +652,7 @@ def main():
     # the timed kernel chain against the oracle: a prefix of the same workload long enough for the default thresholds to choose the
     # same path as the full-size step (asserted through the plan), compared per key bit for bit
     chain = None
-    if rank == 0 and not sharded and not args.no_check and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not sharded and not args.no_check and not args.no_cpu_baseline:
         import numpy as np
         import oracle as orc
 
@@ -631,7 +679,7 @@ def main():
         line = {
             "metric": "Grows/sec hash group-by-sum, 1e9 int64 rows x 1e6 keys", "value": value, "unit": "Grows/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": f"group_by(int64 key).agg(sum,mean,count), {n_total:.3g} rows / {nkeys:.3g} keys"
                                    + (", 1 GPU" if world == 1 else f", row-range sharded over {world} GPUs (RCCL exchange)"),
                        "rows": n_total, "keys": nkeys, "rows_per_gpu": n_local, "parity": "bit-exact vs Arrow-order pairwise sum",

@@ -22,7 +22,7 @@ def _last_json(out):
 
 def test_bench_single_gpu_contract():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "3e6", "--keys", "5e3", "--steps", "2", "--warmup", "1",
-                        "--cpu-sample-rows", "1e6"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--cpu-sample-rows", "1e6", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
     assert all(k in d for k in KEYS)
@@ -58,7 +58,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, PDX_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "4e6", "--keys", "2e4", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     d = _last_json(p.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["rows_per_gpu"] == 2_000_000 and d["cpu_baseline"] is None
@@ -72,9 +72,34 @@ def test_bench_two_ranks_without_a_launcher():
     child processes and rank 0 prints the one JSON line (gloo rehearsal: both ranks share this box's GPU)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PDX_BENCH_BACKEND"] = "gloo"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "4e6", "--keys", "2e4", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "4e6", "--keys", "2e4", "--steps", "2", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     d = _last_json(p.stdout)
     assert d["n_gpus"] == 2 and d["config"]["rows_per_gpu"] == 2_000_000 and d["config"]["path"] == "sharded-c-abi"
     assert d["check"]["groups"] == 20_000 and all(v for v in d["check"].values() if isinstance(v, bool))
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """a plain run (no --full) times the headline step only and leaves the rest of the line null; --dump-outputs writes what the last
+    timed step returned, bit for bit the oracle's group-by of the same seeded inputs"""
+    import numpy as np
+
+    import oracle as orc
+
+    rows, nkeys = 3_000_000, 5_000
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", str(rows), "--keys", str(nkeys), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _last_json(p.stdout)
+    assert all(k in d for k in KEYS) and d["full"] is False and d["steps"] == 3 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and abs(d["value"] - rows / d["ms_per_step"] / 1e6) < 1e-9 * d["value"]
+    assert d["roofline"]["dominant_kernel"]["launches_per_step"] > 0
+    assert all(d[k] is None for k in ("cpu_baseline", "check", "chain_check", "secondary", "general_keys_hash_path"))
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("group_keys", "sum", "mean", "count")}
+    assert sorted(os.listdir(tmp_path)) == ["count.npy", "group_keys.npy", "mean.npy", "sum.npy"]
+    assert all(a.dtype == np.float64 and a.shape == (nkeys,) for a in got.values())
+    ek, es, em, ec = orc.groupby_sum_mean_count(orc.synth_keys(0, rows, nkeys), orc.synth_vals(0, rows))
+    assert np.array_equal(got["group_keys"], ek.astype(np.float64)) and np.array_equal(got["count"], ec.astype(np.float64))
+    assert np.array_equal(got["sum"].view(np.uint64), es.view(np.uint64)) and np.array_equal(got["mean"].view(np.uint64), em.view(np.uint64))

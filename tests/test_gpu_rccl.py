@@ -141,7 +141,7 @@ def test_bench_under_torchrun_nccl():
         env = dict(os.environ, PDX_BENCH_FORCE_DIST="1", PDX_DIST_FORCE_COLLECTIVES="1", PDX_BENCH_DIST=which)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-               "--rows", "2e7", "--keys", "1e5", "--no-cpu-baseline"]
+               "--rows", "2e7", "--keys", "1e5", "--no-cpu-baseline", "--full"]
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -55,7 +55,13 @@ typedef enum pdx_dtype {
   PDX_FLOAT64 = 1,
   PDX_BOOL = 2,         /* bit-packed, LSB first */
   PDX_UINT64 = 3,
-  PDX_TIMESTAMP_NS = 4  /* int64 nanoseconds since epoch */
+  PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
+  /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter and pdx_concat; every other entry point returns
+   * PDX_NOT_IMPLEMENTED naming the dtype.  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
+   * widened (exactly) in v.f64. */
+  PDX_INT32 = 5,
+  PDX_FLOAT32 = 6
 } pdx_dtype;
 
 /* immutable input column (mirrors the fields of arrow::ArrayData the kernels read) */
@@ -207,6 +213,20 @@ int pdx_cast_f64(const pdx_column* a, int checked, pdx_mut_column* out, void* st
 /* Replaces CallFunction("power", {array, Datum(double)}): Series::pow / DataFrame::pow (src/dataframe.cpp:267-270).  Integer input
  * is cast to float64 as in pdx_unary(SQRT); out: PDX_FLOAT64 = pow(a, exponent), last-place caveat as for EXP. */
 int pdx_power(const pdx_column* a, double exponent, pdx_mut_column* out, void* stream);
+
+/* ---------------------------------------------------------------- 32-bit columns (PDX_INT32, PDX_FLOAT32)
+ * pdx_binary / pdx_compare / pdx_if_else follow Arrow's implicit promotion (Arrow C++ 25, tests/golden/narrow_golden.npz):
+ *   int32 (+) int32 -> int32 (wraps; shifts: an amount < 0 or >= 31 returns the left operand), float32 (+) float32 -> float32
+ *   (rounded in fp32), int32 (+) int64 -> int64, int32 / float32 (+) float64 -> float64 (exact), int32 / int64 (+) float32 ->
+ *   float32 through a CHECKED cast: a valid integer outside +-2^24 fails the call with PDX_INVALID "Integer value ... not in
+ *   range: -16777216 to 16777216" (the first such row is named).
+ * pdx_unary: NEGATE / ABS / SIGN / BIT_NOT keep int32 (SIGN of float32 stays float32); SQRT of int32 -> float64, SQRT / EXP of
+ *   float32 -> float32.
+ * pdx_aggregate: sum(int32) -> int64 (exact); sum(float32) -> float64 (each value widened, then the float64 pairwise tree);
+ *   mean -> float64; min / max keep the input dtype; count -> int64. */
+/* Arrow's safe Cast between numeric columns: int32 -> int64 / float64, float32 -> float64 (exact), int32 / int64 -> float32 (checked
+ * as above), and the identity for any supported dtype.  out->dtype names the target; nulls are carried over. */
+int pdx_cast(const pdx_column* a, pdx_mut_column* out, void* stream);
 
 /* ---------------------------------------------------------------- whole-array aggregates
  * Replaces CallFunction("sum"|"mean"|"min"|"max"|"count", {array}, ScalarAggregateOptions{skip_nulls=true,

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("PDX_LIB_PATH") or os.path.join(_HERE, "csrc", "libpdx
 # enums (include/pdx/abi.h)
 OK, INVALID, INDEX_ERROR, OOM, DEVICE, NOT_IMPLEMENTED = range(6)
 INT64, FLOAT64, BOOL, UINT64, TIMESTAMP_NS = range(5)
+INT32, FLOAT32 = 5, 6  # 4 bytes per value (include/pdx/abi.h)
 ADD, SUB, MUL, DIV = range(4)
 BIT_OR, BIT_AND, BIT_XOR, SHIFT_LEFT, SHIFT_RIGHT = range(4, 9)
 EQ, NE, LT, LE, GT, GE = range(6)
@@ -86,6 +87,7 @@ ABI_SYMBOLS = {
     "pdx_if_else": (C.c_int, [_COL, _COL, _COL, C.c_int, _MUT, _P]),
     "pdx_unary": (C.c_int, [C.c_int, _COL, _MUT, _P]),
     "pdx_cast_f64": (C.c_int, [_COL, C.c_int, _MUT, _P]),
+    "pdx_cast": (C.c_int, [_COL, _MUT, _P]),
     "pdx_power": (C.c_int, [_COL, C.c_double, _MUT, _P]),
     "pdx_aggregate": (C.c_int, [C.c_int, _COL, C.POINTER(PdxScalar), _P]),
     "pdx_filter_count": (C.c_int, [_COL, C.c_int, C.POINTER(C.c_int64), _P]),

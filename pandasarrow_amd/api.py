@@ -67,8 +67,18 @@ def _take_filled(cols, idx, fill_value):
     filled = []
     for c in outs:
         is_float = isinstance(fv, (float, np.floating))
+        have = "double" if is_float else "int64"
+        if c.dtype in (L.INT32, L.FLOAT32):
+            # a 4-byte column takes the fill as a scalar of its own type (a python int must fit int32); the result keeps the width
+            fits = (c.dtype == L.FLOAT32) == is_float and (is_float or -2**31 <= int(fv) < 2**31)
+            if not fits:
+                raise L.PdxError(L.INVALID, f"Cannot append scalar of type {have} to builder for type {'float' if c.dtype == L.FLOAT32 else 'int32'}")
+            fcol = Column.from_numpy(np.array([fv], np.float32 if is_float else np.int32), dtype=c.dtype)
+            r = K.if_else(present, c, fcol, b_scalar=True)
+            assert r.dtype == c.dtype
+            filled.append(r)
+            continue
         if c.dtype == L.BOOL or (c.dtype == L.FLOAT64) != is_float:
-            have = "double" if is_float else "int64"
             want = {L.FLOAT64: "double", L.BOOL: "bool", L.UINT64: "uint64", L.TIMESTAMP_NS: "timestamp[ns]"}.get(c.dtype, "int64")
             raise L.PdxError(L.INVALID, f"Cannot append scalar of type {have} to builder for type {want}")
         view = Column(L.INT64, c.length, c.values, c.validity, c.offset, c.null_count) if c.dtype in (L.UINT64, L.TIMESTAMP_NS) else c
@@ -127,14 +137,23 @@ class Scalar:
 
 
 class Series:
-    def __init__(self, values, valid=None, index=None, name="", is_index=False):
+    def __init__(self, values, valid=None, index=None, name="", is_index=False, dtype=None):
+        """dtype: None infers it (float32 arrays stay float32, int32 arrays widen to int64); L.INT32 / L.FLOAT32 keep 4-byte values."""
         if isinstance(values, Column):
             self.col = values
         else:
             a = np.asarray(values)
-            if a.dtype == np.float64 and valid is None and np.isnan(a).any():
+            if dtype == L.FLOAT32:
+                a = a.astype(np.float32)
+            elif dtype == L.INT32 and a.size:  # no silent truncation or wrap: Arrow refuses both when it builds an int32 array
+                whole = a.dtype.kind in "iub" or (a.dtype.kind == "f" and bool(np.all(np.isfinite(a))) and bool(np.all(a == np.trunc(a))))
+                if not whole or a.min() < -2**31 or a.max() >= 2**31:
+                    raise L.PdxError(L.INVALID, "Series(dtype=int32): values must be integers in [-2^31, 2^31)")
+            elif dtype not in (None, L.INT64, L.FLOAT64, L.UINT64, L.BOOL, L.TIMESTAMP_NS):
+                raise L.PdxError(L.INVALID, f"Series: unknown dtype {dtype}")
+            if a.dtype in (np.float64, np.float32) and valid is None and np.isnan(a).any():
                 valid = ~np.isnan(a)  # ArrayT<T>::Make: NaN -> null on construction (src/core.h:404-436)
-            self.col = Column.from_numpy(a, valid)
+            self.col = Column.from_numpy(a, valid, dtype=dtype)
         self.index = index  # Column or None (implicit range)
         self.name = name
         self.is_index = is_index
@@ -182,7 +201,7 @@ class Series:
             return False
         if a.length == 0:
             return True
-        ai, bi = (Column(L.INT64, c.length, c.values, None, c.offset) for c in (a, b))  # labels compare as 64-bit patterns
+        ai, bi = (_label_bits(c) for c in (a, b))  # labels compare as bit patterns of their own width
         return K.filter_count(K.compare(L.EQ, ai, bi)) == a.length
 
     def reindex(self, new_index, fill_value=None):
@@ -523,7 +542,9 @@ class DataFrame:
         self._check_one_dtype()
         tot, cnt = 0.0, 0
         for c in self.cols:
-            v, k = K.aggregate(L.AGG_SUM, c if c.dtype == L.FLOAT64 else K.cast_f64(c, checked=False))  # (Arrow's mean: static_cast<double> per value)
+            # (Arrow's mean: static_cast<double> per value; 4-byte columns widen exactly)
+            d = c if c.dtype == L.FLOAT64 else K.cast(c, L.FLOAT64) if c.dtype in (L.INT32, L.FLOAT32) else K.cast_f64(c, checked=False)
+            v, k = K.aggregate(L.AGG_SUM, d)
             if v is None:
                 continue
             tot, cnt = tot + v, cnt + k
@@ -905,6 +926,10 @@ def concat(frames, axis="index", join="outer", ignore_index=False, sort=False):
         dts = {c.dtype for c in have if c is not None}
         if dts <= {L.INT64, L.FLOAT64}:
             dt = L.FLOAT64 if L.FLOAT64 in dts else L.INT64
+        elif dts <= {L.INT64, L.FLOAT64, L.INT32, L.FLOAT32}:  # a 4-byte column: Arrow's common numeric type
+            dt = L.INT32
+            for d in dts:
+                dt = K.promote_dtype(dt, d)
         elif len(dts) == 1:
             dt = next(iter(dts))
         else:
@@ -913,8 +938,10 @@ def concat(frames, axis="index", join="outer", ignore_index=False, sort=False):
         for f, c in zip(frames, have):
             if c is None:
                 c = K.null_column(dt, f.num_rows())
-            elif c.dtype != dt:  # arrow::compute::Cast(column, double) with default (safe) options, src/concat.cpp:127
+            elif c.dtype != dt and c.dtype == L.INT64 and dt == L.FLOAT64:  # arrow::compute::Cast(column, double), safe options, src/concat.cpp:127
                 c = K.cast_f64(c, checked=True)
+            elif c.dtype != dt:  # (the same safe cast from or to a 4-byte dtype)
+                c = K.cast(c, dt)
             parts.append(c)
         cols.append(K.concat(parts))
     if join == "inner":
@@ -940,6 +967,11 @@ def _scalars_to_column(vals):
     return Column.from_numpy(arr, None if ok.all() else ok)
 
 
+def _label_bits(c: Column) -> Column:
+    """the labels of an index column as integers of the same width (4-byte columns as int32, everything else as int64)"""
+    return Column(L.INT32 if c.dtype in (L.INT32, L.FLOAT32) else L.INT64, c.length, c.values, None, c.offset)
+
+
 def _frame_index(f):
     return f.index if f.index is not None else Column(L.UINT64, f.num_rows(), torch.arange(max(f.num_rows(), 1), dtype=torch.int64, device=K._device()), None)
 
@@ -949,7 +981,7 @@ def _same_labels(a: Column, b: Column):
         return False
     if a.length == 0:
         return True
-    ai, bi = (Column(L.INT64, c.length, c.values, None, c.offset) for c in (a, b))
+    ai, bi = (_label_bits(c) for c in (a, b))
     return K.filter_count(K.compare(L.EQ, ai, bi)) == a.length
 
 

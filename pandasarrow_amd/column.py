@@ -14,7 +14,9 @@ import torch
 
 from . import _lib as L
 
-_TORCH_DT = {L.INT64: torch.int64, L.FLOAT64: torch.float64, L.UINT64: torch.int64, L.TIMESTAMP_NS: torch.int64, L.BOOL: torch.uint8}
+_TORCH_DT = {L.INT64: torch.int64, L.FLOAT64: torch.float64, L.UINT64: torch.int64, L.TIMESTAMP_NS: torch.int64, L.BOOL: torch.uint8,
+             L.INT32: torch.int32, L.FLOAT32: torch.float32}
+_HOST_DT = {L.FLOAT64: np.float64, L.UINT64: np.uint64, L.INT32: np.int32, L.FLOAT32: np.float32}  # (default: int64)
 
 
 def _device():
@@ -59,7 +61,8 @@ class Column:
     # ---- construction -------------------------------------------------------------------------------------
     @staticmethod
     def from_numpy(a, valid=None, dtype=None, offset=0):
-        """Host -> device.  ``offset`` prepends junk rows to exercise Arrow slice offsets."""
+        """Host -> device.  ``offset`` prepends junk rows to exercise Arrow slice offsets.  A float32 array stays FLOAT32; an int32
+        array widens to INT64 unless ``dtype=L.INT32`` asks for the native width."""
         a = np.asarray(a)
         dev = _device()
         if dtype is None:
@@ -67,6 +70,8 @@ class Column:
                 dtype = L.BOOL
             elif a.dtype == np.float64:
                 dtype = L.FLOAT64
+            elif a.dtype == np.float32:
+                dtype = L.FLOAT32
             elif a.dtype == np.uint64:
                 dtype = L.UINT64
             elif a.dtype.kind in "iu":
@@ -80,10 +85,11 @@ class Column:
         if dtype == L.BOOL:
             vals = torch.from_numpy(pack_bits_host(a.astype(bool), offset)).to(dev)
         else:
-            host = a.astype(np.float64 if dtype == L.FLOAT64 else np.int64 if dtype != L.UINT64 else np.uint64)
+            host = a.astype(_HOST_DT.get(dtype, np.int64))
             if offset:
                 host = np.concatenate([np.full(offset, 77, host.dtype), host])
-            vals = torch.from_numpy(np.ascontiguousarray(host).view(np.float64 if dtype == L.FLOAT64 else np.int64).copy()).to(dev)
+            view = {L.FLOAT64: np.float64, L.INT32: np.int32, L.FLOAT32: np.float32}.get(dtype, np.int64)
+            vals = torch.from_numpy(np.ascontiguousarray(host).view(view).copy()).to(dev)
         vbits = None
         if valid is not None:
             vbits = torch.from_numpy(pack_bits_host(valid, offset)).to(dev)
@@ -144,7 +150,20 @@ def _scalar_column(x, like_float):
     return Column.from_numpy(np.array([x], np.int64))
 
 
+_NARROW = (L.INT32, L.FLOAT32)
+
+
+def promote_dtype(da, db):
+    """Arrow's implicit numeric promotion (include/pdx/abi.h): float64 > float32 > int64 > int32."""
+    for dt in (L.FLOAT64, L.FLOAT32, L.INT64):
+        if dt in (da, db):
+            return dt
+    return L.INT32 if (da, db) == (L.INT32, L.INT32) else L.INT64
+
+
 def _promoted(a, b):
+    if a.dtype in _NARROW or b.dtype in _NARROW:
+        return promote_dtype(a.dtype, b.dtype)
     return L.FLOAT64 if L.FLOAT64 in (a.dtype, b.dtype) else L.INT64
 
 
@@ -197,16 +216,17 @@ def invert(a: Column) -> Column:
 def null_column(dtype, n) -> Column:
     """n nulls of `dtype` (device-side zeros: values and validity)."""
     nbytes = _bitmap_bytes(n)
-    vdt = torch.uint8 if dtype == L.BOOL else (torch.float64 if dtype == L.FLOAT64 else torch.int64)
+    vdt = _TORCH_DT.get(dtype, torch.int64)
     vals = torch.zeros(max(nbytes if dtype == L.BOOL else n, 1), dtype=vdt, device=_device())
     return Column(dtype, n, vals, torch.zeros(nbytes, dtype=torch.uint8, device=_device()), 0, n)
 
 
-def if_else(cond: Column, a, b) -> Column:
-    """cond ? a : b (pdx_if_else); a or b may be a python scalar / None (null scalar)."""
+def if_else(cond: Column, a, b, b_scalar=False) -> Column:
+    """cond ? a : b (pdx_if_else); a or b may be a python scalar / None (null scalar), or b a length-1 Column broadcast as the scalar
+    (b_scalar=True)."""
     lib = L.load()
     like_float = any(isinstance(x, Column) and x.dtype == L.FLOAT64 for x in (a, b)) or any(isinstance(x, float) for x in (a, b))
-    side = L.SCALAR_NONE
+    side = L.SCALAR_RHS if b_scalar else L.SCALAR_NONE
     if not isinstance(b, Column):
         b, side = _scalar_column(b, like_float), L.SCALAR_RHS
     elif not isinstance(a, Column):
@@ -221,7 +241,12 @@ def unary(op, a: Column) -> Column:
     """negate / abs / sign / sqrt / exp / bit_wise_not of one column (pdx_unary)."""
     lib = L.load()
     to_f64 = op in (L.SQRT, L.EXP)
-    out_dt = L.FLOAT64 if to_f64 else (L.INT64 if (op == L.SIGN and a.dtype != L.FLOAT64) else a.dtype)
+    if a.dtype == L.FLOAT32:
+        out_dt = L.FLOAT32
+    elif a.dtype == L.INT32:
+        out_dt = L.FLOAT64 if to_f64 else L.INT64 if op == L.SIGN else L.INT32
+    else:
+        out_dt = L.FLOAT64 if to_f64 else (L.INT64 if (op == L.SIGN and a.dtype != L.FLOAT64) else a.dtype)
     out = Column.empty(out_dt, a.length, with_validity=a.has_nulls())
     ca, m = a.c(), out.mut()
     L.check(lib.pdx_unary(int(op), C.byref(ca), C.byref(m), _stream()))
@@ -233,6 +258,15 @@ def cast_f64(a: Column, checked=True) -> Column:
     out = Column.empty(L.FLOAT64, a.length, with_validity=a.has_nulls())
     ca, m = a.c(), out.mut()
     L.check(L.load().pdx_cast_f64(C.byref(ca), int(bool(checked)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def cast(a: Column, dtype) -> Column:
+    """Arrow's safe Cast between numeric dtypes (pdx_cast): int32 -> int64 / float64, float32 -> float64, int32 / int64 -> float32
+    (checked: +-2^24), int64 -> float64 (checked: +-2^53)."""
+    out = Column.empty(dtype, a.length, with_validity=a.has_nulls())
+    ca, m = a.c(), out.mut()
+    L.check(L.load().pdx_cast(C.byref(ca), C.byref(m), _stream()))
     return out._adopt(m)
 
 
@@ -253,7 +287,7 @@ def aggregate(kind, a: Column):
     L.check(lib.pdx_aggregate(kind, C.byref(ca), C.byref(s), _stream()))
     if not s.is_valid:
         return None, int(s.count)
-    if s.dtype == L.FLOAT64:
+    if s.dtype in (L.FLOAT64, L.FLOAT32):  # (a float32 result is held widened)
         return float(s.v.f64), int(s.count)
     return int(s.v.i64), int(s.count)
 
@@ -308,7 +342,13 @@ def scatter(cols, idx: Column, outs):
 
 
 def concat(parts) -> Column:
+    """Row concat; parts that mix a 4-byte dtype with another numeric one are first cast to the common type (pdx_cast)."""
     lib = L.load()
+    if any(p.dtype in _NARROW for p in parts) and len({p.dtype for p in parts}) > 1:
+        dt = parts[0].dtype
+        for p in parts[1:]:
+            dt = promote_dtype(dt, p.dtype)
+        parts = [p if p.dtype == dt else cast(p, dt) for p in parts]
     total = sum(p.length for p in parts)
     out = Column.empty(parts[0].dtype, total, with_validity=any(p.has_nulls() for p in parts))
     m = out.mut()
@@ -365,7 +405,7 @@ def reindex_indices(old_index: Column, new_index: Column) -> Column:
 
 
 # ---------------------------------------------------------------- group-by / resample handles
-_AGG_OUT_DT = {L.AGG_MEAN: lambda dt: L.FLOAT64, L.AGG_COUNT: lambda dt: L.INT64, L.AGG_SUM: lambda dt: dt, L.AGG_MIN: lambda dt: dt,
+_AGG_OUT_DT = {L.AGG_MEAN: lambda dt: L.FLOAT64, L.AGG_COUNT: lambda dt: L.INT64, L.AGG_SUM: lambda dt: {L.INT32: L.INT64, L.FLOAT32: L.FLOAT64}.get(dt, dt), L.AGG_MIN: lambda dt: dt,
                L.AGG_MAX: lambda dt: dt, L.AGG_VARIANCE: lambda dt: L.FLOAT64, L.AGG_STDDEV: lambda dt: L.FLOAT64,
                L.AGG_PRODUCT: lambda dt: dt, L.AGG_FIRST: lambda dt: dt, L.AGG_LAST: lambda dt: dt,
                L.AGG_ALL: lambda dt: L.BOOL, L.AGG_ANY: lambda dt: L.BOOL, L.AGG_COUNT_DISTINCT: lambda dt: L.INT64}

@@ -434,12 +434,14 @@ __global__ void k_count_valid(const uint8_t* __restrict__ valid, int64_t off, in
   if ((threadIdx.x & 63) == 0 && vc) atomicAdd(total, vc);
 }
 
-__global__ void __launch_bounds__(256) k_sum_i64(const int64_t* __restrict__ v, const uint8_t* __restrict__ valid, int64_t off,
+// T = int32_t: each value sign-extended into the int64 accumulator (Arrow: sum(int32) -> int64)
+template <typename T>
+__global__ void __launch_bounds__(256) k_sum_i64(const T* __restrict__ v, const uint8_t* __restrict__ valid, int64_t off,
                                                  int64_t n, unsigned long long* __restrict__ total) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   unsigned long long acc = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    if (!valid || bit_get(valid, off + i)) acc += (unsigned long long)v[i];
+    if (!valid || bit_get(valid, off + i)) acc += (unsigned long long)(int64_t)v[i];
   for (int d = 32; d > 0; d >>= 1) acc += __shfl_down(acc, d, 64);
   if ((threadIdx.x & 63) == 0) atomicAdd(total, acc);  // wrap-around add is order independent
 }
@@ -614,11 +616,11 @@ static int pairwise_sum_host(const pdx_column* a, double* sum_out, int64_t* coun
 using namespace pdx;
 
 extern "C" int pdx_aggregate(int kind, const pdx_column* a, pdx_scalar* out, void* stream) {
-  PDX_TRY(check_column(a, "pdx_aggregate"));
+  PDX_TRY(check_column(a, "pdx_aggregate", true));
   if (!out) return fail(PDX_INVALID, "pdx_aggregate: null output");
   if (kind < PDX_AGG_SUM || kind > PDX_AGG_COUNT) return fail(PDX_INVALID, "pdx_aggregate: unknown kind");
-  const bool is_f = a->dtype == PDX_FLOAT64;
-  if (!is_f && a->dtype != PDX_INT64 && !(kind == PDX_AGG_COUNT) && !((kind == PDX_AGG_MIN || kind == PDX_AGG_MAX) && a->dtype == PDX_TIMESTAMP_NS))
+  const bool is_f = a->dtype == PDX_FLOAT64 || a->dtype == PDX_FLOAT32;
+  if (!is_f && a->dtype != PDX_INT64 && a->dtype != PDX_INT32 && !(kind == PDX_AGG_COUNT) && !((kind == PDX_AGG_MIN || kind == PDX_AGG_MAX) && a->dtype == PDX_TIMESTAMP_NS))
     return fail(PDX_NOT_IMPLEMENTED, "pdx_aggregate: only int64/float64 columns are supported");
   hipStream_t st = as_stream(stream);
   Scratch s;
@@ -639,7 +641,10 @@ extern "C" int pdx_aggregate(int kind, const pdx_column* a, pdx_scalar* out, voi
     if (is_f || kind == PDX_AGG_MEAN) {
       double sum = 0;
       int64_t cnt = 0;
-      if (is_f) PDX_TRY(pairwise_sum_host<double>(a, &sum, &cnt, s, st));
+      // 4-byte columns are read as they are and each value is widened in registers before the float64 tree
+      if (a->dtype == PDX_FLOAT64) PDX_TRY(pairwise_sum_host<double>(a, &sum, &cnt, s, st));
+      else if (a->dtype == PDX_FLOAT32) PDX_TRY(pairwise_sum_host<float>(a, &sum, &cnt, s, st));
+      else if (a->dtype == PDX_INT32) PDX_TRY(pairwise_sum_host<int32_t>(a, &sum, &cnt, s, st));
       else PDX_TRY(pairwise_sum_host<int64_t>(a, &sum, &cnt, s, st));
       out->dtype = PDX_FLOAT64;
       out->count = cnt;
@@ -653,8 +658,11 @@ extern "C" int pdx_aggregate(int kind, const pdx_column* a, pdx_scalar* out, voi
     unsigned long long* total = s.get<unsigned long long>(1);
     PDX_SCRATCH_CHECK(s);
     PDX_HIP(hipMemsetAsync(total, 0, sizeof(*total), st));
-    if (n)
-      hipLaunchKernelGGL(k_sum_i64, dim3(grid_for(n, 256, 8)), dim3(256), 0, st, static_cast<const int64_t*>(a->values) + a->offset,
+    if (n && a->dtype == PDX_INT32)
+      hipLaunchKernelGGL(k_sum_i64<int32_t>, dim3(grid_for(n, 256, 8)), dim3(256), 0, st, static_cast<const int32_t*>(a->values) + a->offset,
+                         validity_or_null(a), a->offset, n, total);
+    else if (n)
+      hipLaunchKernelGGL(k_sum_i64<int64_t>, dim3(grid_for(n, 256, 8)), dim3(256), 0, st, static_cast<const int64_t*>(a->values) + a->offset,
                          validity_or_null(a), a->offset, n, total);
     PDX_LAUNCH_CHECK();
     unsigned long long h = 0;
@@ -671,7 +679,19 @@ extern "C" int pdx_aggregate(int kind, const pdx_column* a, pdx_scalar* out, voi
   out->count = cnt;
   out->dtype = a->dtype;
   if (cnt == 0) return PDX_OK;  // null
-  if (is_f) {
+  if (a->dtype == PDX_FLOAT32) {  // the extreme stays float32 (held widened in v.f64)
+    MinMaxPartial<float> r;
+    PDX_TRY(minmax_impl<float>(static_cast<const float*>(a->values) + a->offset, validity_or_null(a), a->offset, n, &r, s, st,
+                               /*max_last=*/cnt < n));
+    out->is_valid = 1;
+    if (r.rmin < 0) out->v.f64 = __builtin_nan("");  // every valid value is NaN
+    else out->v.f64 = (double)(kind == PDX_AGG_MIN ? r.vmin : r.vmax);
+  } else if (a->dtype == PDX_INT32) {
+    MinMaxPartial<int> r;
+    PDX_TRY(minmax_impl<int>(static_cast<const int*>(a->values) + a->offset, validity_or_null(a), a->offset, n, &r, s, st));
+    out->is_valid = 1;
+    out->v.i64 = kind == PDX_AGG_MIN ? r.vmin : r.vmax;
+  } else if (is_f) {
     MinMaxPartial<double> r;
     PDX_TRY(minmax_impl<double>(static_cast<const double*>(a->values) + a->offset, validity_or_null(a), a->offset, n, &r, s, st,
                                 /*max_last=*/cnt < n));

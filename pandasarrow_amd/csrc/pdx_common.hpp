@@ -175,7 +175,12 @@ struct ErrFlag {
   long long payload;
 };
 
-int check_column(const pdx_column* c, const char* what);
+// narrow_ok: the entry point handles the 4-byte dtypes (PDX_INT32 / PDX_FLOAT32).  Every other caller gets PDX_NOT_IMPLEMENTED naming
+// the dtype: its kernels address 8-byte elements and would read past the end of a 4-byte column.
+int check_column(const pdx_column* c, const char* what, bool narrow_ok = false);
+inline bool is_narrow(int dt) { return dt == PDX_INT32 || dt == PDX_FLOAT32; }
+inline int dtype_bytes(int dt) { return is_narrow(dt) ? 4 : 8; }
+const char* dtype_name(int dt);
 inline bool is_int_like(int dt) { return dt == PDX_INT64 || dt == PDX_UINT64 || dt == PDX_TIMESTAMP_NS; }
 inline const uint8_t* validity_or_null(const pdx_column* c) {
   return (c->validity && c->null_count != 0) ? static_cast<const uint8_t*>(c->validity) : nullptr;

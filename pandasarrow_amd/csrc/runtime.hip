@@ -23,8 +23,22 @@ int hip_fail(hipError_t e, const char* what) {
   return e == hipErrorOutOfMemory ? PDX_OOM : PDX_DEVICE;
 }
 
-int check_column(const pdx_column* c, const char* what) {
+const char* dtype_name(int dt) {
+  switch (dt) {
+    case PDX_INT64: return "int64";
+    case PDX_FLOAT64: return "float64";
+    case PDX_BOOL: return "bool";
+    case PDX_UINT64: return "uint64";
+    case PDX_TIMESTAMP_NS: return "timestamp[ns]";
+    case PDX_INT32: return "int32";
+    case PDX_FLOAT32: return "float32";
+    default: return "unknown";
+  }
+}
+
+int check_column(const pdx_column* c, const char* what, bool narrow_ok) {
   if (!c) return fail(PDX_INVALID, std::string(what) + ": null column");
+  if (!narrow_ok && is_narrow(c->dtype)) return fail(PDX_NOT_IMPLEMENTED, std::string(what) + ": dtype " + dtype_name(c->dtype) + " is not supported");
   if (c->length < 0 || c->offset < 0) return fail(PDX_INVALID, std::string(what) + ": negative length/offset");
   if (c->length > 0 && !c->values) return fail(PDX_INVALID, std::string(what) + ": null values pointer");
   return PDX_OK;

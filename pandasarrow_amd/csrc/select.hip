@@ -22,8 +22,23 @@ struct GatherCols {
   int64_t src_off[kMaxCols];
   uint64_t* dst[kMaxCols];
   uint8_t* dst_valid[kMaxCols];       // or nullptr
+  uint8_t narrow[kMaxCols];           // 1: 4-byte values (PDX_INT32 / PDX_FLOAT32); src / dst then address 4-byte elements
   int ncols;
 };
+// one value of column `col` (a 4-byte value travels in the low half); the branch is uniform: one column per iteration
+__device__ __forceinline__ uint64_t ld_col(const GatherCols& c, int col, int64_t i) {
+  return c.narrow[col] ? (uint64_t)reinterpret_cast<const uint32_t*>(c.src[col])[i] : c.src[col][i];
+}
+__device__ __forceinline__ void st_col(const GatherCols& c, int col, int64_t i, uint64_t v) {
+  if (c.narrow[col]) reinterpret_cast<uint32_t*>(c.dst[col])[i] = (uint32_t)v;
+  else c.dst[col][i] = v;
+}
+static void set_col_ptrs(GatherCols& g, int c, const pdx_column& col, const pdx_mut_column& out) {
+  const int64_t w = dtype_bytes(col.dtype);
+  g.narrow[c] = w == 4;
+  g.src[c] = reinterpret_cast<const uint64_t*>(static_cast<const char*>(col.values) + col.offset * w);
+  g.dst[c] = static_cast<uint64_t*>(out.values);
+}
 
 // idx[j] < 0  => emit a null row.  idx_valid (bitmap, optional) marks null indices.  Bounds are checked against n_src.
 // A wave owns kGatherU consecutive 64-row output words per iteration and issues the index loads of all of them, then per
@@ -73,7 +88,7 @@ __global__ void __launch_bounds__(256) k_gather(GatherCols c, const IDX* __restr
 #pragma unroll
         for (int u = 0; u < kGatherU; ++u) {
           ok[cc][u] = col < c.ncols && k[u] >= 0 && (!c.src_valid[col] || bit_get(c.src_valid[col], c.src_off[col] + k[u]));
-          v[cc][u] = ok[cc][u] ? c.src[col][k[u]] : 0ull;
+          v[cc][u] = ok[cc][u] ? ld_col(c, col, k[u]) : 0ull;
         }
       }
 #pragma unroll
@@ -83,7 +98,7 @@ __global__ void __launch_bounds__(256) k_gather(GatherCols c, const IDX* __restr
 #pragma unroll
         for (int u = 0; u < kGatherU; ++u) {
           const int64_t w = g * kGatherU + u;
-          if (in[u]) c.dst[col][(w << 6) + lane] = v[cc][u];
+          if (in[u]) st_col(c, col, (w << 6) + lane, v[cc][u]);
           if (c.dst_valid[col]) {
             uint64_t bal = __ballot(ok[cc][u]);
             if (lane == 0 && w < nwords) {
@@ -118,7 +133,7 @@ __global__ void __launch_bounds__(256) k_scatter(GatherCols c, const int64_t* __
     }
     for (int col = 0; col < c.ncols; ++col) {
       bool ok = !c.src_valid[col] || bit_get(c.src_valid[col], c.src_off[col] + j);
-      c.dst[col][k] = c.src[col][j];
+      st_col(c, col, k, ld_col(c, col, j));
       if (c.dst_valid[col]) {
         unsigned int* word = reinterpret_cast<unsigned int*>(c.dst_valid[col]) + (k >> 5);
         unsigned int bit = 1u << (k & 31);
@@ -207,7 +222,7 @@ __global__ void __launch_bounds__(kCompactBlock) k_filter_stream(GatherCols c, c
 #pragma unroll
       for (int s = 0; s < kCompactItems; ++s) {
         const bool p = ((sel[s] >> lane) & 1) && col < c.ncols;
-        v[cc][s] = p ? c.src[col][base + s * 64 + lane] : 0ull;
+        v[cc][s] = p ? ld_col(c, col, base + s * 64 + lane) : 0ull;
       }
     }
 #pragma unroll
@@ -238,7 +253,7 @@ __global__ void __launch_bounds__(kCompactBlock) k_filter_stream(GatherCols c, c
                                  (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)nulls_v);
           if ((sel[s] >> lane) & 1) {
             const int64_t o = pos + __popcll(sel[s] & lt);
-            c.dst[col][o] = ((nulls >> lane) & 1) ? 0ull : v[cc][s];
+            st_col(c, col, o, ((nulls >> lane) & 1) ? 0ull : v[cc][s]);
           }
           for (uint64_t rem = nulls; rem; rem &= rem - 1) {
             const int b = __ffsll((unsigned long long)rem) - 1;
@@ -253,7 +268,7 @@ __global__ void __launch_bounds__(kCompactBlock) k_filter_stream(GatherCols c, c
       } else {
 #pragma unroll
         for (int s = 0; s < kCompactItems; ++s) {
-          if ((sel[s] >> lane) & 1) c.dst[col][pos + __popcll(sel[s] & lt)] = v[cc][s];
+          if ((sel[s] >> lane) & 1) st_col(c, col, pos + __popcll(sel[s] & lt), v[cc][s]);
           pos += __popcll(sel[s]);
         }
       }
@@ -279,7 +294,7 @@ static int fill_cols(GatherCols& g, const pdx_column* cols, int ncols, pdx_mut_c
   if (ncols < 1 || ncols > kMaxCols) return fail(PDX_INVALID, std::string(what) + ": between 1 and 16 columns per call");
   g.ncols = ncols;
   for (int c = 0; c < ncols; ++c) {
-    PDX_TRY(check_column(&cols[c], what));
+    PDX_TRY(check_column(&cols[c], what, true));
     if (cols[c].dtype == PDX_BOOL) return fail(PDX_NOT_IMPLEMENTED, std::string(what) + ": boolean columns are not supported yet");
     if (cols[c].length != src_len) return fail(PDX_INVALID, std::string(what) + ": all columns must have the same length");
     if (outs[c].length < out_len) return fail(PDX_INVALID, std::string(what) + ": output too small");
@@ -287,10 +302,9 @@ static int fill_cols(GatherCols& g, const pdx_column* cols, int ncols, pdx_mut_c
     if (out_len && !outs[c].values) return fail(PDX_INVALID, std::string(what) + ": null output buffer");
     const uint8_t* sv = validity_or_null(&cols[c]);
     if ((sv || forced_nulls) && !outs[c].validity) return fail(PDX_INVALID, std::string(what) + ": nulls possible but an output has no validity buffer");
-    g.src[c] = static_cast<const uint64_t*>(cols[c].values) + cols[c].offset;
+    set_col_ptrs(g, c, cols[c], outs[c]);
     g.src_valid[c] = sv;
     g.src_off[c] = cols[c].offset;
-    g.dst[c] = static_cast<uint64_t*>(outs[c].values);
     g.dst_valid[c] = static_cast<uint8_t*>(outs[c].validity);
   }
   return PDX_OK;
@@ -483,16 +497,15 @@ int pdx_scatter(const pdx_column* cols, int ncols, const pdx_column* indices, pd
   g.ncols = ncols;
   int64_t n_dst = outs[0].length;
   for (int c = 0; c < ncols; ++c) {
-    PDX_TRY(check_column(&cols[c], "pdx_scatter"));
+    PDX_TRY(check_column(&cols[c], "pdx_scatter", true));
     if (cols[c].length != m) return fail(PDX_INVALID, "pdx_scatter: columns and indices must have the same length");
     if (outs[c].dtype != cols[c].dtype || cols[c].dtype == PDX_BOOL) return fail(PDX_INVALID, "pdx_scatter: dtype mismatch / boolean unsupported");
     if (outs[c].length != n_dst || (n_dst && !outs[c].values)) return fail(PDX_INVALID, "pdx_scatter: bad output column");
     const uint8_t* sv = validity_or_null(&cols[c]);
     if (sv && !outs[c].validity) return fail(PDX_INVALID, "pdx_scatter: nulls possible but an output has no validity buffer");
-    g.src[c] = static_cast<const uint64_t*>(cols[c].values) + cols[c].offset;
+    set_col_ptrs(g, c, cols[c], outs[c]);
     g.src_valid[c] = sv;
     g.src_off[c] = cols[c].offset;
-    g.dst[c] = static_cast<uint64_t*>(outs[c].values);
     g.dst_valid[c] = static_cast<uint8_t*>(outs[c].validity);
     outs[c].null_count = -1;
   }
@@ -518,7 +531,7 @@ int pdx_concat(const pdx_column* parts, int nparts, pdx_mut_column* out, void* s
   int64_t total = 0;
   bool any_valid = false;
   for (int q = 0; q < nparts; ++q) {
-    PDX_TRY(check_column(&parts[q], "pdx_concat"));
+    PDX_TRY(check_column(&parts[q], "pdx_concat", true));
     if (parts[q].dtype != parts[0].dtype) return fail(PDX_INVALID, "pdx_concat: parts must share one dtype (promote first)");
     if (parts[q].dtype == PDX_BOOL) return fail(PDX_NOT_IMPLEMENTED, "pdx_concat: boolean columns are not supported yet");
     cp.valid[q] = validity_or_null(&parts[q]);
@@ -534,10 +547,11 @@ int pdx_concat(const pdx_column* parts, int nparts, pdx_mut_column* out, void* s
   out->length = total;
   out->null_count = 0;
   if (total == 0) return PDX_OK;
+  const size_t w = (size_t)dtype_bytes(parts[0].dtype);
   for (int q = 0; q < nparts; ++q)
     if (parts[q].length)
-      PDX_HIP(hipMemcpyAsync(static_cast<uint64_t*>(out->values) + cp.start[q], static_cast<const uint64_t*>(parts[q].values) + parts[q].offset,
-                             (size_t)parts[q].length * 8, hipMemcpyDeviceToDevice, st));
+      PDX_HIP(hipMemcpyAsync(static_cast<char*>(out->values) + cp.start[q] * w, static_cast<const char*>(parts[q].values) + parts[q].offset * w,
+                             (size_t)parts[q].length * w, hipMemcpyDeviceToDevice, st));
   if (out->validity) {
     Scratch s;
     unsigned long long* nulls = s.get<unsigned long long>(1);

@@ -123,6 +123,21 @@ def test_elementwise_large_vs_oracle(px):
         assert np.array_equal(px.K.compare(op, A, B).to_numpy()[0], orc.compare(op, a, b)[0])
     m1, m2 = px.K.compare(4, A, 0.5), px.K.compare(2, B, 0.0)
     assert np.array_equal(px.K.logical(0, m1, m2).to_numpy()[0], (a > 0.5) & (b < 0.0))
+    # slices at an odd element offset are not 16-byte aligned: the row-per-lane loops (main part and tail), on one or both sides
+    ia = (np.arange(n, dtype=np.int64) * 7919) % 200_003 - 100_000
+    ib = (np.arange(n, dtype=np.int64) * 104_729) % 999 + 1
+    for x, y in ((a, b), (ia, ib), (ia, b)):
+        for ox, oy in ((3, 0), (0, 1), (1, 5)):
+            X, Y = px.Column.from_numpy(x, offset=ox), px.Column.from_numpy(y, offset=oy)
+            for op in OPS.values():
+                got = px.K.binary(op, X, Y).to_numpy()[0]
+                exp = orc.binary(op, x, y)[0]
+                if got.dtype == np.float64:
+                    assert_f64_bits(got, exp, what=f"op{op} offsets {ox},{oy}", nan_bits=True)
+                else:
+                    assert np.array_equal(got, exp), (op, ox, oy)
+            for op in CMPS.values():
+                assert np.array_equal(px.K.compare(op, X, Y).to_numpy()[0], orc.compare(op, x, y)[0]), (op, ox, oy)
 
 
 # ------------------------------------------------------------------ whole-array aggregates

@@ -296,6 +296,23 @@ def test_mixed_type_promotion_is_arrows_checked_cast(px):
     # same dtypes never pay the check; int64 (op) int64 wraps as before
     got, _ = K.binary(L.ADD, px.Column.from_numpy(bad), px.Column.from_numpy(bad)).to_numpy()
     assert np.array_equal(got, bad + bad)
+    # two offending valid rows many waves apart (and an offending null before both): the message names the FIRST, as Arrow's does
+    n = 1_000_000
+    big = np.arange(n, dtype=np.int64) % 1000
+    valid = np.ones(n, bool)
+    big[5], valid[5] = 2**60, False
+    big[123_457], big[876_543] = 2**53 + 1, -(2**53) - 7
+    c, fb = px.Column.from_numpy(big, valid), px.Column.from_numpy(np.full(n, 0.5))
+    for call in (lambda: K.binary(L.ADD, c, fb), lambda: K.compare(L.LT, fb, c), lambda: K.if_else(K.compare(L.GT, fb, 1.0, True), c, fb),
+                 lambda: K.cast_f64(c, checked=True), lambda: K.unary(L.SQRT, c)):
+        with pytest.raises(L.PdxError, match=r"Integer value 9007199254740993 not in range: -9007199254740992 to 9007199254740992"):
+            call()
+    got, ok = K.cast_f64(c, checked=False).to_numpy()
+    assert np.array_equal(ok, valid) and np.array_equal(got[valid], big[valid].astype(np.float64))
+    u = big.astype(np.uint64)
+    u[876_543] = 2**60
+    with pytest.raises(L.PdxError, match=r"Integer value 9007199254740993 not in range: 0 to 9007199254740992"):
+        K.unary(L.SQRT, px.Column.from_numpy(u, valid))
 
 
 def test_sort_index_makes_group_results_order_independent(px):

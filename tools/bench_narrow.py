@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Timings of the 32-bit column paths against their 64-bit twins, measured in the same process (not the contract bench): achieved GB/s
-against each op's ALGORITHMIC bytes.  add / greater at 1e9 rows, float32 sum, filter of 1e8 rows x 9 int32 columns, take.
+against each op's ALGORITHMIC bytes.  add / greater at 1e9 rows, float32 sum, float64 add at an odd offset, int64 + float64 add, the
+int64 -> float64 cast (checked and not), filter of 1e8 rows x 9 int32 columns, take.
 Usage: python tools/bench_narrow.py [--scale 1.0]   (prints one JSON line per op)."""
 import argparse
 import os
@@ -49,6 +50,22 @@ def main():
                 report(f"sum_{K._TORCH_DT[dt]}".replace("torch.", ""), n, w * n, timeit(lambda: K.aggregate(L.AGG_SUM, a), reps=5))
             del a, b, out, bo
             torch.cuda.empty_cache()
+    # float64 add of two slices at an odd element offset (not 16-byte aligned: the row-per-lane loop), and a mixed int64 + float64 add
+    # (Arrow's checked cast of the int64 operand)
+    lib, st = L.load(), K._stream()
+    a, b = device_col(L.FLOAT64, n + 1, 1), device_col(L.FLOAT64, n + 1, 2)
+    sa, sb, out = K.Column(L.FLOAT64, n, a.values, None, 1), K.Column(L.FLOAT64, n, b.values, None, 1), K.Column.empty(L.FLOAT64, n)
+    ca, cb, m = sa.c(), sb.c(), out.mut()
+    report("add_float64_offset1", n, 24 * n, timeit(lambda: L.check(lib.pdx_binary(L.ADD, ca, cb, 0, m, st)), reps=5))
+    del a, sa
+    ia = device_col(L.INT64, n, 3)
+    ca, cb = ia.c(), K.Column(L.FLOAT64, n, b.values).c()
+    report("add_int64_float64", n, 24 * n, timeit(lambda: L.check(lib.pdx_binary(L.ADD, ca, cb, 0, m, st)), reps=5))
+    # int64 -> float64 cast: Arrow's checked cast and the unchecked one of the frame mean (pdx_cast_f64, checked = 1 / 0)
+    for checked in (1, 0):
+        report(f"cast_f64_int64_checked{checked}", n, 16 * n, timeit(lambda: L.check(lib.pdx_cast_f64(ca, checked, m, st)), reps=5))
+    del ia, b, sb, out
+    torch.cuda.empty_cache()
     nf = int(1e8 * sc)
     mask = K.compare(L.GT, device_col(L.FLOAT64, nf, 9), 0.0, scalar=True)
     for dt in (L.INT32, L.INT64):

@@ -57,7 +57,8 @@ typedef enum pdx_dtype {
   PDX_UINT64 = 3,
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
-   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter and pdx_concat; every other entry point returns
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null and pdx_shift; every
+   * other entry point returns
    * PDX_NOT_IMPLEMENTED naming the dtype.  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
    * widened (exactly) in v.f64. */
   PDX_INT32 = 5,
@@ -107,6 +108,8 @@ typedef enum pdx_binary_op {
 } pdx_binary_op;
 /* element-wise functions of one column (pdx_unary) */
 typedef enum pdx_unary_op { PDX_NEGATE = 0, PDX_ABS = 1, PDX_SIGN = 2, PDX_SQRT = 3, PDX_EXP = 4, PDX_BIT_NOT = 5 } pdx_unary_op;
+/* running accumulations of one column (pdx_cumulative) */
+typedef enum pdx_cum_op { PDX_CUM_SUM = 0, PDX_CUM_PROD = 1, PDX_CUM_MAX = 2, PDX_CUM_MIN = 3 } pdx_cum_op;
 typedef enum pdx_compare_op { PDX_EQ = 0, PDX_NE = 1, PDX_LT = 2, PDX_LE = 3, PDX_GT = 4, PDX_GE = 5 } pdx_compare_op;
 typedef enum pdx_logical_op { PDX_AND = 0, PDX_OR = 1 } pdx_logical_op;
 /* which operand of pdx_binary / pdx_compare is a length-1 column that is broadcast (the `b_is_scalar` argument) */
@@ -227,6 +230,45 @@ int pdx_power(const pdx_column* a, double exponent, pdx_mut_column* out, void* s
 /* Arrow's safe Cast between numeric columns: int32 -> int64 / float64, float32 -> float64 (exact), int32 / int64 -> float32 (checked
  * as above), and the identity for any supported dtype.  out->dtype names the target; nulls are carried over. */
 int pdx_cast(const pdx_column* a, pdx_mut_column* out, void* stream);
+
+/* ---------------------------------------------------------------- cumulative scans, fill_null, shift (order-dependent transforms)
+ * Common rules: out->dtype equals a's, out->length >= a->length; input validity and offset are arbitrary (bit offsets that are not
+ * multiples of 8 included); length is int64 (no 2^31 limit); an empty input gives PDX_OK and length 0.  out->validity may be NULL only
+ * when the result cannot hold a null (PDX_INVALID otherwise); out->null_count is exact; value bytes under a null output row are
+ * unspecified.  `out` must not alias `a` (in place is not supported: equal value pointers are refused with PDX_INVALID).  The calls are
+ * asynchronous on `stream` except where they read the null count back: pdx_cumulative and pdx_fill_null when the input carries a validity
+ * bitmap with null_count != 0, pdx_shift when such an input keeps at least one of its rows.
+ *
+ * pdx_cumulative replaces CumulativeSum / Prod / Max / Min(array, CumulativeOptions{start, skip_nulls}): Series::cumsum / cumprod / cummax /
+ * cummin (src/series.cpp:321-339).  a: PDX_INT64, PDX_UINT64, PDX_FLOAT64, PDX_INT32, PDX_FLOAT32; PDX_TIMESTAMP_NS and PDX_BOOL return
+ * PDX_NOT_IMPLEMENTED "Function 'cumulative_sum' has no kernel matching input types (timestamp[ns])".  Integer sums and products wrap;
+ * float32 accumulates in fp32.  `start` is cast to the column's type by Arrow's safe cast before anything is launched: PDX_INVALID "Float
+ * value 1.500000 was truncated converting to int64" for a fraction, NaN or a value outside the type's range; float32 rounds it to nearest.
+ * The reference always passes a start, so it is a required argument (Arrow's own default for cumulative_max of float64,
+ * numeric_limits<double>::min(), is not reproduced).  skip_nulls != 0: a null row is null in the output and the accumulation goes on behind
+ * it; skip_nulls == 0: every row from the first null on is null.  max / min skip NaN values (a NaN start included) and the LATER operand
+ * wins a tie (signed zeros).
+ * Bit-exact against the reference: integer sum / product, max / min of every dtype.  NOT bit-reproducible: the float64 / float32 SUM and
+ * PRODUCT -- the reference adds left to right, and a chain of rounded additions has no parallel evaluation with the same bits.  Their contract:
+ * (1) deterministic: the bits are a function of values, validity and start alone (the evaluation tree is defined by the row index relative
+ * to the slice's first row: any offset, stream, run or PDX_SCAN_CHUNK_ROWS gives the same bits); (2) equal to the reference wherever every
+ * order of evaluation gives one result (all partial results exactly representable); (3) within the a-priori bound of any summation order,
+ * |got_i - exact_i| <= (k_i - 1) u / (1 - (k_i - 1) u) * (|start| + sum |x_j|), k_i = valid terms up to row i with the start, u = 2^-53
+ * (2^-24) -- for the product the same factor times |exact_i|, absent overflow / underflow; (4) NaN and infinities from the VALUES appear where
+ * the reference has them (NaN sign / payload not compared); an intermediate overflow of finite values is the exception: the reference's
+ * running sum can reach infinity where a tree's partial sums stay finite, and the other way round.
+ *
+ * pdx_fill_null replaces fill_null_forward / fill_null_backward: Series / DataFrame::ffill / bfill (src/series.cpp:748-750,
+ * src/dataframe.cpp:1292-1294).  a: the five dtypes above and PDX_TIMESTAMP_NS (PDX_BOOL: PDX_NOT_IMPLEMENTED).  Leading (backward:
+ * trailing) nulls stay null; a slice is filled from its own rows only.
+ *
+ * pdx_shift replaces Series::shift(periods, fill) (src/series.cpp:702-736): out[i] = a[i - periods] where that row exists, else the fill
+ * (fill == NULL or fill->is_valid == 0: null).  periods > 0 moves rows toward the end, 0 is a copy, |periods| >= length gives a column of
+ * fills (the reference's builder fails there).  Same dtypes as pdx_fill_null; fill->dtype must equal a's (PDX_INVALID), 4-byte values as
+ * pdx_scalar documents (v.i64 sign-extended, v.f64 widened).  One pass over the data. */
+int pdx_cumulative(int op, const pdx_column* a, double start, int skip_nulls, pdx_mut_column* out, void* stream);
+int pdx_fill_null(int backward, const pdx_column* a, pdx_mut_column* out, void* stream);
+int pdx_shift(const pdx_column* a, int64_t periods, const pdx_scalar* fill /* NULL: nulls */, pdx_mut_column* out, void* stream);
 
 /* ---------------------------------------------------------------- whole-array aggregates
  * Replaces CallFunction("sum"|"mean"|"min"|"max"|"count", {array}, ScalarAggregateOptions{skip_nulls=true,

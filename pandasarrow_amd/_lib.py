@@ -22,6 +22,7 @@ BIT_OR, BIT_AND, BIT_XOR, SHIFT_LEFT, SHIFT_RIGHT = range(4, 9)
 EQ, NE, LT, LE, GT, GE = range(6)
 AND, OR = range(2)
 NEGATE, ABS, SIGN, SQRT, EXP, BIT_NOT = range(6)
+CUM_SUM, CUM_PROD, CUM_MAX, CUM_MIN = range(4)  # pdx_cum_op
 SCALAR_NONE, SCALAR_RHS, SCALAR_LHS = range(3)  # pdx_scalar_side: which operand of pdx_binary / pdx_compare is broadcast
 AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT = range(5)
 AGG_VARIANCE, AGG_STDDEV, AGG_PRODUCT, AGG_FIRST, AGG_LAST = range(5, 10)  # group-by only (include/pdx/abi.h)
@@ -89,6 +90,9 @@ ABI_SYMBOLS = {
     "pdx_cast_f64": (C.c_int, [_COL, C.c_int, _MUT, _P]),
     "pdx_cast": (C.c_int, [_COL, _MUT, _P]),
     "pdx_power": (C.c_int, [_COL, C.c_double, _MUT, _P]),
+    "pdx_cumulative": (C.c_int, [C.c_int, _COL, C.c_double, C.c_int, _MUT, _P]),
+    "pdx_fill_null": (C.c_int, [C.c_int, _COL, _MUT, _P]),
+    "pdx_shift": (C.c_int, [_COL, C.c_int64, C.POINTER(PdxScalar), _MUT, _P]),
     "pdx_aggregate": (C.c_int, [C.c_int, _COL, C.POINTER(PdxScalar), _P]),
     "pdx_filter_count": (C.c_int, [_COL, C.c_int, C.POINTER(C.c_int64), _P]),
     "pdx_filter": (C.c_int, [_COL, C.c_int, _COL, C.c_int, _MUT, _P]),

@@ -257,6 +257,21 @@ class Series:
     def sqrt(self): return self._wrap(K.unary(L.SQRT, self.col))
     def exp(self): return self._wrap(K.unary(L.EXP, self.col))
     def pow(self, x): return self._wrap(K.power(self.col, x))
+
+    # ---- order-dependent transforms: Cumulative*(array, {start, skip_nulls}) src/series.cpp:321-339, fill_null_* 748-750, shift 702-736;
+    # index and name are kept
+    def _keep(self, col): return Series(col, index=self.index, name=self.name)
+    def cumsum(self, start=0, skip_nulls=True): return self._keep(K.cumulative(L.CUM_SUM, self.col, start, skip_nulls))
+    def cumprod(self, start=1, skip_nulls=True): return self._keep(K.cumulative(L.CUM_PROD, self.col, start, skip_nulls))
+    def cummax(self, start, skip_nulls=True): return self._keep(K.cumulative(L.CUM_MAX, self.col, start, skip_nulls))
+    def cummin(self, start, skip_nulls=True): return self._keep(K.cumulative(L.CUM_MIN, self.col, start, skip_nulls))
+    def ffill(self): return self._keep(K.fill_null(self.col))
+    def bfill(self): return self._keep(K.fill_null(self.col, backward=True))
+
+    def shift(self, periods=1, fill_value=None):
+        if isinstance(fill_value, Scalar):
+            fill_value = fill_value.value
+        return self._keep(K.shift(self.col, periods, fill_value))
     # ---- comparisons (src/series.cpp:247-257)
     def __lt__(self, o): return self._cmp(L.LT, o)
     def __le__(self, o): return self._cmp(L.LE, o)
@@ -510,6 +525,10 @@ class DataFrame:
     def sqrt(self): return self._unary(L.SQRT)
     def exp(self): return self._unary(L.EXP)
     def pow(self, x): return self._like([K.power(c, x) for c in self.cols])
+
+    # fill_null_forward / fill_null_backward over every column (src/dataframe.cpp:1292-1294); a bool column raises the library's error
+    def ffill(self): return self._like([K.fill_null(c) for c in self.cols])
+    def bfill(self): return self._like([K.fill_null(c, backward=True) for c in self.cols])
 
     # ---- NDFrame::sum/mean/min/max/count on a DataFrame (src/ndframe.cpp:119-220): GetInternalArray() is ONE ChunkedArray whose
     # chunks are the columns (src/ndframe.h:329-335), so the aggregate runs over every value of the frame.  Arrow reduces a

@@ -278,6 +278,40 @@ def power(a: Column, exponent: float) -> Column:
     return out._adopt(m)
 
 
+# ---------------------------------------------------------------- cumulative scans, fill_null, shift
+def cumulative(op, a: Column, start, skip_nulls=True) -> Column:
+    """cumulative_sum / prod / max / min (pdx_cumulative): the input's dtype; `start` goes through Arrow's safe cast to it."""
+    out = Column.empty(a.dtype, a.length, with_validity=a.has_nulls())
+    ca, m = a.c(), out.mut()
+    L.check(L.load().pdx_cumulative(int(op), C.byref(ca), float(start), int(bool(skip_nulls)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def fill_null(a: Column, backward=False) -> Column:
+    """fill_null_forward / fill_null_backward (pdx_fill_null)."""
+    out = Column.empty(a.dtype, a.length, with_validity=a.has_nulls())
+    ca, m = a.c(), out.mut()
+    L.check(L.load().pdx_fill_null(int(bool(backward)), C.byref(ca), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def shift(a: Column, periods, fill=None) -> Column:
+    """out[i] = a[i - periods]; rows without a source take `fill` (None: null) (pdx_shift)."""
+    s = None
+    if fill is not None:
+        s = L.PdxScalar(a.dtype, 1)
+        if a.dtype in (L.FLOAT64, L.FLOAT32):
+            s.v.f64 = float(fill)
+        elif a.dtype == L.UINT64:
+            s.v.u64 = int(fill)
+        else:
+            s.v.i64 = int(fill)
+    out = Column.empty(a.dtype, a.length, with_validity=a.has_nulls() or (fill is None and periods != 0 and a.length > 0))
+    ca, m = a.c(), out.mut()
+    L.check(L.load().pdx_shift(C.byref(ca), int(periods), None if s is None else C.byref(s), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
 # ---------------------------------------------------------------- aggregates
 def aggregate(kind, a: Column):
     """-> (python value | None, count)."""

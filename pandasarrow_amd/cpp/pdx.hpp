@@ -331,6 +331,16 @@ class Series {
   Series sign() const { return wrap(run_unary(PDX_SIGN, m_array)); }
   Series sqrt() const { return wrap(run_unary(PDX_SQRT, m_array)); }
   Series exp() const { return wrap(run_unary(PDX_EXP, m_array)); }
+  // src/series.cpp:321-339, 748-750, 702-736: index and name are kept
+  Series cumsum(double start = 0, bool skip_nulls = true) const { return Series(run_cumulative(PDX_CUM_SUM, m_array, start, skip_nulls), m_index, m_name); }
+  Series cumprod(double start = 1, bool skip_nulls = true) const { return Series(run_cumulative(PDX_CUM_PROD, m_array, start, skip_nulls), m_index, m_name); }
+  Series cummax(double start, bool skip_nulls = true) const { return Series(run_cumulative(PDX_CUM_MAX, m_array, start, skip_nulls), m_index, m_name); }
+  Series cummin(double start, bool skip_nulls = true) const { return Series(run_cumulative(PDX_CUM_MIN, m_array, start, skip_nulls), m_index, m_name); }
+  Series ffill() const { return Series(run_fill_null(m_array, false), m_index, m_name); }
+  Series bfill() const { return Series(run_fill_null(m_array, true), m_index, m_name); }
+  Series shift(int32_t periods = 1, const std::optional<Scalar>& fillValue = std::nullopt) const {
+    return Series(run_shift(m_array, periods, fillValue), m_index, m_name);
+  }
   Series pow(double x) const { return wrap(run_power(m_array, x)); }
 
   // ---- comparisons (src/series.cpp:247-257) and logical (259-261, 319)
@@ -488,6 +498,40 @@ class Series {
     out.null_count = m.null_count;
     return out;
   }
+  // Cumulative{Sum,Prod,Max,Min}(array, CumulativeOptions{start, skip_nulls}), fill_null_forward / backward, shift
+  static Array run_cumulative(int op, const Array& a, double start, bool skip_nulls) {
+    Array out = Array::Empty(a.dtype, a.length, a.has_nulls());
+    auto ca = a.c();
+    auto m = out.mut();
+    ThrowOnFailure(pdx_cumulative(op, &ca, start, skip_nulls ? 1 : 0, &m, nullptr));
+    out.null_count = m.null_count;
+    return out;
+  }
+  static Array run_fill_null(const Array& a, bool backward) {
+    Array out = Array::Empty(a.dtype, a.length, a.has_nulls());
+    auto ca = a.c();
+    auto m = out.mut();
+    ThrowOnFailure(pdx_fill_null(backward ? 1 : 0, &ca, &m, nullptr));
+    out.null_count = m.null_count;
+    return out;
+  }
+  static Array run_shift(const Array& a, int64_t periods, const std::optional<Scalar>& fill) {
+    Array out = Array::Empty(a.dtype, a.length, a.has_nulls() || (!fill && periods != 0 && a.length > 0));
+    auto ca = a.c();
+    auto m = out.mut();
+    pdx_scalar f{};
+    if (fill) {  // an integer literal fills a float64 column as the reference's MakeScalar would
+      f = fill->s;
+      if (a.dtype == PDX_FLOAT64 && f.dtype == PDX_INT64) { f.dtype = PDX_FLOAT64; f.v.f64 = (double)fill->s.v.i64; }
+      if ((a.dtype == PDX_TIMESTAMP_NS || a.dtype == PDX_UINT64) && f.dtype == PDX_INT64) {
+        if (a.dtype == PDX_UINT64 && f.v.i64 < 0) throw std::runtime_error("shift: negative fill value for a uint64 column");
+        f.dtype = a.dtype;  // the same 64 bits
+      }
+    }
+    ThrowOnFailure(pdx_shift(&ca, periods, fill ? &f : nullptr, &m, nullptr));
+    out.null_count = m.null_count;
+    return out;
+  }
   static Array run_power(const Array& a, double x) {
     Array out = Array::Empty(PDX_FLOAT64, a.length, a.has_nulls());
     auto ca = a.c();
@@ -639,6 +683,17 @@ class DataFrame {
   DataFrame unary(int op) const {
     std::vector<Array> out;
     for (auto& c : m_columns) out.push_back(Series::run_unary(op, c));
+    return DataFrame(m_names, out, m_index);
+  }
+  // fill_null_forward / fill_null_backward over every column (src/dataframe.cpp:1292-1294)
+  DataFrame ffill() const {
+    std::vector<Array> out;
+    for (auto& c : m_columns) out.push_back(Series::run_fill_null(c, false));
+    return DataFrame(m_names, out, m_index);
+  }
+  DataFrame bfill() const {
+    std::vector<Array> out;
+    for (auto& c : m_columns) out.push_back(Series::run_fill_null(c, true));
     return DataFrame(m_names, out, m_index);
   }
   DataFrame operator-() const { return unary(PDX_NEGATE); }

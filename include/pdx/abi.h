@@ -57,7 +57,7 @@ typedef enum pdx_dtype {
   PDX_UINT64 = 3,
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
-   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null and pdx_shift; every
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift and pdx_quantile; every
    * other entry point returns
    * PDX_NOT_IMPLEMENTED naming the dtype.  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
    * widened (exactly) in v.f64. */
@@ -277,6 +277,41 @@ int pdx_shift(const pdx_column* a, int64_t periods, const pdx_scalar* fill /* NU
  * Synchronises `stream`. */
 int pdx_aggregate(int kind, const pdx_column* a, pdx_scalar* out, void* stream);
 
+/* ---------------------------------------------------------------- exact quantiles
+ * Replaces CallFunction("quantile", {array}, QuantileOptions{q, interpolation, skip_nulls, min_count}): NDFrame::quantile
+ * (src/ndframe.h:259-263, src/ndframe.cpp:202-212), the per-percentile calls of DataFrame::describe (src/dataframe.cpp:983-1030) and, per
+ * group, GroupBy::quantile (src/group_by.h:123-124, src/dataframe.cpp:1867-1931).  Semantics = Arrow C++ 25.0.0, bit for bit
+ * (tests/golden/quantile_golden.npz):
+ *   - a: PDX_INT64, PDX_UINT64, PDX_FLOAT64, PDX_INT32, PDX_FLOAT32 (pdx_groupby_quantile: the three 8-byte dtypes).  PDX_TIMESTAMP_NS and
+ *     PDX_BOOL return PDX_NOT_IMPLEMENTED "Function 'quantile' has no kernel matching input types (timestamp[ns])".
+ *   - nulls and NaN values take no part; n = number of valid non-NaN values = `count` of the scalar.  The result is null (is_valid = 0 /
+ *     validity bit clear) when n == 0, when fewer than min_count rows are non-null (Arrow counts NaN rows here), or when skip_nulls == 0 and
+ *     the input (the group) holds a null.
+ *   - every q in [0, 1], else (NaN too; Arrow itself lets a NaN q through) PDX_INVALID "Quantile must be between 0 and 1"; nq <= 0: PDX_INVALID "Requires quantile argument"; both
+ *     before anything is launched.
+ *   - with v = the n values ascending, index = (n - 1) * q in double, lo = (uint64) index, f = index - lo, hi = lo + 1 when f != 0 else lo:
+ *       LINEAR   -> float64: f == 0 ? (double) v[lo] : f * (double) v[hi] + (1 - f) * (double) v[lo]   (each product rounded, no FMA)
+ *       MIDPOINT -> float64: f == 0 ? (double) v[lo] : v[lo] / 2 + v[hi] / 2                           (halves first: no overflow)
+ *       LOWER v[lo], HIGHER v[hi], NEAREST f < 0.5 ? v[lo] : f > 0.5 ? v[hi] : v[lo + (lo & 1)]        (a tie goes to the even index)
+ *     LOWER / HIGHER / NEAREST keep the input dtype (4-byte values in a pdx_scalar as pdx_dtype documents).
+ *   - -0.0 and 0.0 are equal in the order: where a result is a zero of a column that holds both, it is the zero that comes first in
+ *     pdx_argsort's stable order, i.e. v's zeros keep their ROW order (Arrow returns whichever zero its nth_element left there).
+ * pdx_quantile: the ranks of all nq quantiles are located from ONE histogram read of the column (64 per read beyond that); unless that read
+ * already settles them (one distinct value) a second read copies out the bins that hold them, and a result that is a zero of a float column
+ * costs a third.  Scratch: the copied bins, in the worst case (every row in one bin, e.g. two distinct values) one key per row, held until
+ * the call returns.  Length is int64 without a 2^31 limit, every
+ * count and rank is 64 bits wide; any offset, validity at any bit offset, null_count -1; deterministic (same bits on any stream / run).
+ * Synchronises `stream` like pdx_aggregate.  outs: nq scalars.
+ * pdx_groupby_quantile: per group the same rule over the group's rows; handles from pdx_groupby_create / pdx_resample_create /
+ * pdx_downsample_create, the handle's row limit.  outs: nq columns of >= G rows, PDX_FLOAT64 (LINEAR / MIDPOINT) or the values' dtype;
+ * validity is required when a group result is null (PDX_INVALID otherwise), null_count is exact.  Neither the bound-column cache nor
+ * pdx_groupby_last_plan is touched. */
+/* arrow::compute::QuantileOptions::Interpolation, same numbering */
+typedef enum pdx_interpolation { PDX_INTERP_LINEAR = 0, PDX_INTERP_LOWER = 1, PDX_INTERP_HIGHER = 2,
+                                 PDX_INTERP_NEAREST = 3, PDX_INTERP_MIDPOINT = 4 } pdx_interpolation;
+int pdx_quantile(const pdx_column* a, const double* q, int nq, int interpolation, int skip_nulls, int64_t min_count,
+                 pdx_scalar* outs /* nq */, void* stream);
+
 /* ---------------------------------------------------------------- filter / take
  * Replaces CallFunction("filter", {RecordBatch, mask}, FilterOptions{EMIT_NULL}) + CallFunction("array_filter",
  * {index, mask}) at src/dataframe.cpp:461-475 and src/series.cpp:130-144.  mask: PDX_BOOL of the same length as
@@ -360,6 +395,9 @@ int64_t pdx_groupby_bound_bytes(const pdx_groupby* gb);
  *   reducer=flr_reduce_dense|flr_reduce|flr_wave|seg_reduce|seg_reduce_nullable|none
  *   bound=0|1 [cache=fill|hit] */
 int pdx_groupby_last_plan(const pdx_groupby* gb, char* buf, size_t buf_len);
+/* GroupBy::quantile (src/group_by.h:123-124, src/dataframe.cpp:1867-1931): see "exact quantiles" above. */
+int pdx_groupby_quantile(pdx_groupby* gb, const pdx_column* values, const double* q, int nq, int interpolation,
+                         int skip_nulls, int64_t min_count, pdx_mut_column* outs /* nq columns of >= G rows */, void* stream);
 
 /* ---------------------------------------------------------------- exact multi-GPU fp64 sum (partial-tree exchange)
  * The reference's per-group sum is Arrow's pairwise tree over the group's rows in GLOBAL row order; with row-range shards a

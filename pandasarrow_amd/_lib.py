@@ -23,6 +23,7 @@ EQ, NE, LT, LE, GT, GE = range(6)
 AND, OR = range(2)
 NEGATE, ABS, SIGN, SQRT, EXP, BIT_NOT = range(6)
 CUM_SUM, CUM_PROD, CUM_MAX, CUM_MIN = range(4)  # pdx_cum_op
+INTERP_LINEAR, INTERP_LOWER, INTERP_HIGHER, INTERP_NEAREST, INTERP_MIDPOINT = range(5)  # pdx_interpolation
 SCALAR_NONE, SCALAR_RHS, SCALAR_LHS = range(3)  # pdx_scalar_side: which operand of pdx_binary / pdx_compare is broadcast
 AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT = range(5)
 AGG_VARIANCE, AGG_STDDEV, AGG_PRODUCT, AGG_FIRST, AGG_LAST = range(5, 10)  # group-by only (include/pdx/abi.h)
@@ -94,6 +95,7 @@ ABI_SYMBOLS = {
     "pdx_fill_null": (C.c_int, [C.c_int, _COL, _MUT, _P]),
     "pdx_shift": (C.c_int, [_COL, C.c_int64, C.POINTER(PdxScalar), _MUT, _P]),
     "pdx_aggregate": (C.c_int, [C.c_int, _COL, C.POINTER(PdxScalar), _P]),
+    "pdx_quantile": (C.c_int, [_COL, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(PdxScalar), _P]),
     "pdx_filter_count": (C.c_int, [_COL, C.c_int, C.POINTER(C.c_int64), _P]),
     "pdx_filter": (C.c_int, [_COL, C.c_int, _COL, C.c_int, _MUT, _P]),
     "pdx_take": (C.c_int, [_COL, C.c_int, _COL, _MUT, _P]),
@@ -113,6 +115,7 @@ ABI_SYMBOLS = {
     "pdx_groupby_bind_limit": (C.c_int, [_P, C.c_size_t]),
     "pdx_groupby_bound_bytes": (C.c_int64, [_P]),
     "pdx_groupby_last_plan": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
+    "pdx_groupby_quantile": (C.c_int, [_P, _COL, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int64, _MUT, _P]),
     "pdx_groupby_group_values": (C.c_int, [_P, _COL, _P, C.POINTER(_P)]),
     "pdx_grouped_destroy": (C.c_int, [_P]),
     "pdx_grouped_counts": (C.c_int, [_P, _P, _P]),

@@ -302,6 +302,13 @@ class Series:
     def max(self): return self._agg(L.AGG_MAX)
     def count(self): return self._agg(L.AGG_COUNT)
 
+    def quantile(self, q=0.5, interpolation="linear", skip_nulls=True, min_count=0):
+        """NDFrame::quantile (src/ndframe.h:259-263, src/ndframe.cpp:202-212): Arrow's exact quantile.  A list of q gives a list of Scalars
+        from one call (one histogram read locates all their ranks)."""
+        many = isinstance(q, (list, tuple))
+        res = [Scalar(v, c) for v, c in K.quantile(self.col, list(q) if many else [q], interpolation, skip_nulls, min_count)]
+        return res if many else res[0]
+
     def count_na(self):
         """NDFrame::count_na (src/ndframe.cpp:119-126): CountOptions::ONLY_NULL."""
         return self.size() - int(K.aggregate(L.AGG_COUNT, self.col)[0])
@@ -568,6 +575,11 @@ class DataFrame:
                 continue
             tot, cnt = tot + v, cnt + k
         return Scalar(tot / cnt if cnt else None, cnt)
+
+    def quantile(self, q=0.5, interpolation="linear", skip_nulls=True, min_count=0):
+        """The quantile of every column, by column name: the per-column meaning DataFrame::describe uses (src/dataframe.cpp:983-1030).  (The
+        reference's own DataFrame::quantile passes QuantileOptions to "stddev", src/dataframe.cpp:209-213; that slip is not reproduced.)"""
+        return {nm: Series(c).quantile(q, interpolation, skip_nulls, min_count) for nm, c in zip(self.names, self.cols)}
 
     def _extreme(self, kind):
         self._check_one_dtype()
@@ -877,6 +889,22 @@ class GroupBy:
     def all(self, args): return self._agg_frame(L.AGG_ALL, args)
     def any(self, args): return self._agg_frame(L.AGG_ANY, args)
     def count_distinct(self, args): return self._agg_frame(L.AGG_COUNT_DISTINCT, args)
+
+    def quantile(self, args, q=0.5, interpolation="linear", skip_nulls=True, min_count=0):
+        """GroupBy::quantile (src/group_by.h:123-124, src/dataframe.cpp:1867-1931): one column name and one q -> Series indexed by the unique
+        keys; a list of names and a list of q -> DataFrame whose column args[i] uses q[i], as the reference pairs them."""
+        uniq = self.unique()
+        if isinstance(args, str):
+            if isinstance(q, (list, tuple)):
+                raise L.PdxError(L.INVALID, "GroupBy.quantile: one column takes one quantile")
+            c = self.df.cols[self.df.names.index(args)]
+            return Series(self._h.quantile(c, [q], interpolation, skip_nulls, min_count)[0], index=uniq, name=args)
+        names = list(args)
+        qs = list(q) if isinstance(q, (list, tuple)) else [q]
+        if len(qs) != len(names):
+            raise L.PdxError(L.INVALID, "GroupBy.quantile: args and quantiles differ in length")
+        outs = [self._h.quantile(self.df.cols[self.df.names.index(nm)], [x], interpolation, skip_nulls, min_count)[0] for nm, x in zip(names, qs)]
+        return DataFrame(dict(zip(names, outs)), index=uniq)
 
     def min_max(self, args):
         """GroupBy::min_max (src/dataframe.cpp:1602-1696): arrow::compute::MinMax per group.  One column name -> frame with

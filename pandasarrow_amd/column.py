@@ -326,6 +326,38 @@ def aggregate(kind, a: Column):
     return int(s.v.i64), int(s.count)
 
 
+INTERPOLATIONS = {"linear": L.INTERP_LINEAR, "lower": L.INTERP_LOWER, "higher": L.INTERP_HIGHER, "nearest": L.INTERP_NEAREST,
+                  "midpoint": L.INTERP_MIDPOINT}
+
+
+def interpolation_code(interpolation) -> int:
+    if isinstance(interpolation, str):
+        if interpolation not in INTERPOLATIONS:
+            raise L.PdxError(L.INVALID, f"unknown interpolation {interpolation!r}")
+        return INTERPOLATIONS[interpolation]
+    return int(interpolation)
+
+
+def quantile(a: Column, qs, interpolation=L.INTERP_LINEAR, skip_nulls=True, min_count=0):
+    """Exact quantiles of one column; the ranks of all of them are located by one histogram read of it (pdx_quantile).  -> list of (python value | None, count)."""
+    qs = [float(x) for x in qs]
+    qarr = (C.c_double * max(len(qs), 1))(*qs)
+    outs = (L.PdxScalar * max(len(qs), 1))()
+    ca = a.c()
+    L.check(L.load().pdx_quantile(C.byref(ca), qarr, len(qs), interpolation_code(interpolation), int(bool(skip_nulls)), int(min_count), outs, _stream()))
+    res = []
+    for s in outs[:len(qs)]:
+        if not s.is_valid:
+            res.append((None, int(s.count)))
+        elif s.dtype in (L.FLOAT64, L.FLOAT32):  # (a float32 result is held widened)
+            res.append((float(s.v.f64), int(s.count)))
+        elif s.dtype == L.UINT64:
+            res.append((int(s.v.u64), int(s.count)))
+        else:
+            res.append((int(s.v.i64), int(s.count)))
+    return res
+
+
 # ---------------------------------------------------------------- filter / take / concat
 def _col_array(cols):
     arr = (L.PdxColumn * len(cols))(*[c.c() for c in cols])
@@ -574,6 +606,19 @@ class GroupByHandle:
         karr = (C.c_int * len(kinds))(*kinds)
         cv = values.c()
         L.check(L.load().pdx_groupby_agg(self._h, C.byref(cv), karr, len(kinds), marr, _stream()))
+        return [o._adopt(marr[i]) for i, o in enumerate(outs)]
+
+    def quantile(self, values: Column, qs, interpolation=L.INTERP_LINEAR, skip_nulls=True, min_count=0):
+        """Per group the exact quantiles of its values (pdx_groupby_quantile).  -> list of Columns (G rows, group-id order), one per q."""
+        qs = [float(x) for x in qs]
+        interp = interpolation_code(interpolation)
+        G = self.num_groups
+        dt = L.FLOAT64 if interp in (L.INTERP_LINEAR, L.INTERP_MIDPOINT) else values.dtype
+        outs = [Column.empty(dt, G, with_validity=True) for _ in qs]
+        marr = _mut_array(outs) if outs else None
+        qarr = (C.c_double * max(len(qs), 1))(*qs)
+        cv = values.c()
+        L.check(L.load().pdx_groupby_quantile(self._h, C.byref(cv), qarr, len(qs), interp, int(bool(skip_nulls)), int(min_count), marr, _stream()))
         return [o._adopt(marr[i]) for i, o in enumerate(outs)]
 
 

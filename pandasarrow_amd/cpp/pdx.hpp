@@ -190,6 +190,10 @@ struct Scalar {
   }
 };
 
+// arrow::compute::QuantileOptions::Interpolation (pdx_interpolation)
+enum class Interpolation { LINEAR = PDX_INTERP_LINEAR, LOWER = PDX_INTERP_LOWER, HIGHER = PDX_INTERP_HIGHER, NEAREST = PDX_INTERP_NEAREST,
+                           MIDPOINT = PDX_INTERP_MIDPOINT };
+
 class DataFrame;
 struct GroupBy;
 struct Resampler;
@@ -384,6 +388,17 @@ class Series {
   Scalar min() const { return agg(PDX_AGG_MIN); }
   Scalar max() const { return agg(PDX_AGG_MAX); }
   Scalar count() const { return agg(PDX_AGG_COUNT); }
+  // NDFrame::quantile (src/ndframe.h:259-263, src/ndframe.cpp:202-212): Arrow's exact quantile; several q share one call (one histogram read locates all their ranks)
+  std::vector<Scalar> quantiles(const std::vector<double>& q, Interpolation interpolation = Interpolation::LINEAR, bool skip_nulls = true,
+                                uint32_t min_count = 0) const {
+    std::vector<pdx_scalar> out(q.size() ? q.size() : 1);
+    auto c = m_array.c();
+    ThrowOnFailure(pdx_quantile(&c, q.data(), (int)q.size(), (int)interpolation, skip_nulls ? 1 : 0, (int64_t)min_count, out.data(), nullptr));
+    return std::vector<Scalar>(out.begin(), out.begin() + (std::ptrdiff_t)q.size());
+  }
+  Scalar quantile(double q = 0.5, Interpolation interpolation = Interpolation::LINEAR, bool skip_nulls = true, uint32_t min_count = 0) const {
+    return quantiles({q}, interpolation, skip_nulls, min_count)[0];
+  }
   // NDFrame::count_na / all / any / nunique (src/ndframe.cpp:110-127), Series::unique (src/series.h:380)
   int64_t count_na() const { return size() - count().as<int64_t>(); }
   bool all() const { return bool_counts("all").second == 0; }
@@ -777,6 +792,14 @@ class DataFrame {
   template <typename R> DataFrame operator*(const R& o) const { return binary(PDX_MUL, o); }
   template <typename R> DataFrame operator/(const R& o) const { return binary(PDX_DIV, o); }
 
+  // The quantile of every column, by column name -- the per-column meaning DataFrame::describe uses (src/dataframe.cpp:983-1030).  (The
+  // reference's own DataFrame::quantile hands QuantileOptions to "stddev", src/dataframe.cpp:209-213: not reproduced.)
+  std::map<std::string, Scalar> quantile(double q = 0.5, Interpolation interpolation = Interpolation::LINEAR, bool skip_nulls = true,
+                                         uint32_t min_count = 0) const {
+    std::map<std::string, Scalar> out;
+    for (size_t i = 0; i < m_columns.size(); ++i) out[m_names[i]] = Series(m_columns[i]).quantile(q, interpolation, skip_nulls, min_count);
+    return out;
+  }
   // NDFrame::sum on a frame (src/ndframe.h:329-335): every column (chunk) summed, totals added in column order
   Scalar sum() const {
     bool first = true, is_f = false;
@@ -1086,6 +1109,29 @@ struct GroupBy {
   DataFrame product(const std::vector<std::string>& a) const { return agg(a, PDX_AGG_PRODUCT); }
   DataFrame first(const std::vector<std::string>& a) const { return agg(a, PDX_AGG_FIRST); }
   DataFrame last(const std::vector<std::string>& a) const { return agg(a, PDX_AGG_LAST); }
+  // GroupBy::quantile (src/group_by.h:123-124, src/dataframe.cpp:1867-1931): per group Arrow's exact quantile of the group's rows; with
+  // several columns, column args[i] uses qs[i] (options[i], src/dataframe.cpp:1874-1892)
+  Array quantile_array(const std::string& arg, double q, Interpolation interpolation, bool skip_nulls, uint32_t min_count) const {
+    const Array& v = df.m_columns[(size_t)df.column_index(arg)];
+    const bool to_f64 = interpolation == Interpolation::LINEAR || interpolation == Interpolation::MIDPOINT;
+    Array out = Array::Empty(to_f64 ? (int)PDX_FLOAT64 : v.dtype, (int64_t)groupSize(), true);
+    auto c = v.c();
+    auto m = out.mut();
+    ThrowOnFailure(pdx_groupby_quantile(handle->h, &c, &q, 1, (int)interpolation, skip_nulls ? 1 : 0, (int64_t)min_count, &m, nullptr));
+    out.null_count = m.null_count;
+    return out;
+  }
+  Series quantile(const std::string& arg, double q = 0.5, Interpolation interpolation = Interpolation::LINEAR, bool skip_nulls = true,
+                  uint32_t min_count = 0) const {
+    return Series(quantile_array(arg, q, interpolation, skip_nulls, min_count), unique(), arg);
+  }
+  DataFrame quantile(const std::vector<std::string>& args, const std::vector<double>& qs, Interpolation interpolation = Interpolation::LINEAR,
+                     bool skip_nulls = true, uint32_t min_count = 0) const {
+    if (args.size() != qs.size()) throw std::runtime_error("GroupBy::quantile: args and quantiles differ in length");
+    std::vector<Array> cols;
+    for (size_t i = 0; i < args.size(); ++i) cols.push_back(quantile_array(args[i], qs[i], interpolation, skip_nulls, min_count));
+    return DataFrame(args, cols, unique());
+  }
 
   // ---- walking the groups (src/group_by.h:39-77; src/dataframe.cpp:1354-1510).  The reference materialises every group's arrays in
   // the constructor (Grouper::MakeGroupings + ApplyGroupings); here the groupings are built on first use (pdx_groupby_groupings) and a

@@ -712,8 +712,10 @@ __device__ __forceinline__ bool hybrid_decode(const uint8_t* p, int64_t pos, int
     const uint32_t h = rd_varint(p, &pos, end);
     if (h & 1) {  // bit-packed run: groups of 8 values, bw bits each, LSB first
       const int64_t cnt = (int64_t)(h >> 1) * 8, bytes = (int64_t)(h >> 1) * bw;
-      if (cnt == 0 || pos + bytes > end + 8) return false;  // (writers may cut the padding of the last group short)
       const int64_t take = cnt < need - done ? cnt : need - done;
+      // every value that is taken must lie inside the stream; the padding behind the last of them may be missing (writers cut the last
+      // group short, by up to 28 bytes at 32 bits), and a run that is short of its values is malformed however few bytes it lacks
+      if (cnt == 0 || pos + ((take * bw + 7) >> 3) > end) return false;
       for (int64_t j = lane; j < take; j += 64) {
         const int64_t bit = j * bw;
         const uint64_t w = ld_u64(p + pos + (bit >> 3));

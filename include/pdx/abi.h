@@ -471,10 +471,60 @@ int pdx_downsample_create(const pdx_column* ts, int64_t multiple, int unit, int 
  * and keys a Resampler's GroupBy on the result (pdx_groupby_create; the labels need not be sorted). */
 typedef enum pdx_calendar_unit {
   PDX_UNIT_NANOSECOND = 0, PDX_UNIT_MICROSECOND = 1, PDX_UNIT_MILLISECOND = 2, PDX_UNIT_SECOND = 3, PDX_UNIT_MINUTE = 4,
-  PDX_UNIT_HOUR = 5, PDX_UNIT_DAY = 6, PDX_UNIT_WEEK = 7, PDX_UNIT_MONTH = 8, PDX_UNIT_QUARTER = 9
+  PDX_UNIT_HOUR = 5, PDX_UNIT_DAY = 6, PDX_UNIT_WEEK = 7, PDX_UNIT_MONTH = 8, PDX_UNIT_QUARTER = 9,
+  PDX_UNIT_YEAR = 10 /* pdx_temporal_between only; rounding to years returns PDX_NOT_IMPLEMENTED */
 } pdx_calendar_unit;
+/* ceil_mode (the rounding mode): PDX_ROUND_FLOOR / PDX_ROUND_CEIL as above (every value other than 0 and 2 is a ceil, as it always
+ * was); PDX_ROUND_NEAREST is Arrow's round_temporal
+ * (DateTimeLike::round, src/series.cpp:672-685): of the floor f and the ceil c of t under the same options it returns c when
+ * t - f >= c - t, else f -- a tie goes up; month / quarter compare the distances in nanoseconds to the first instants of the two
+ * months (pinned by tests/golden/temporal_golden.npz).  ceil_is_strictly_greater is always false (the facades refuse true). */
+typedef enum pdx_round_mode { PDX_ROUND_FLOOR = 0, PDX_ROUND_CEIL = 1, PDX_ROUND_NEAREST = 2 } pdx_round_mode;
 int pdx_round_temporal(int ceil_mode, const pdx_column* ts, int64_t multiple, int unit, int week_starts_monday, int calendar_based_origin,
                        pdx_mut_column* out, void* stream);
+
+/* ---------------------------------------------------------------- the dt accessor: calendar components and *_between
+ * Replaces the Arrow temporal kernels behind Series::dt() (DateTimeLike, src/datetimelike.h; src/series.cpp:1387-1487,
+ * src/dataframe.cpp:904-913).  Input is always PDX_TIMESTAMP_NS without a time zone (anything else: PDX_INVALID); all divisions floor
+ * toward -inf (-1 ns is 1969-12-31 23:59:59.999999999); results are bit-identical to Arrow C++ 25 (tests/golden/temporal_golden.npz).
+ *
+ * pdx_temporal_components: ONE read of ts produces nc columns, 1 <= nc <= 8 (PDX_INVALID otherwise): 8 B read + 8 x nc B written
+ * per row.  components[c] is a pdx_temporal_component, outs[c] the caller's buffer for it, of at least ts->length rows and of the
+ * component's dtype (PDX_INVALID on a mismatch):
+ *   PDX_INT64  : YEAR, MONTH (1-12), DAY (1-31), DAY_OF_WEEK (0 = Monday .. 6 = Sunday: Arrow's default DayOfWeekOptions, which
+ *                is what the reference passes), DAY_OF_YEAR (1-366), HOUR, MINUTE, SECOND, MILLISECOND / MICROSECOND / NANOSECOND
+ *                (0-999 each), QUARTER (1-4), ISO_WEEK, ISO_YEAR, ISO_DAY_OF_WEEK (1 = Monday .. 7), US_WEEK, US_YEAR (weeks from
+ *                Sunday, week 1 holds 4 January), WEEK (week_opts)
+ *   PDX_BOOL   : IS_LEAP_YEAR (bit-packed, stored in whole 64-row words: the values buffer needs 8-byte alignment and
+ *                (length + 7) / 8 bytes)
+ *   PDX_FLOAT64: SUBSECOND = (nanoseconds since the last whole second) / 1e9, one IEEE division
+ * week_opts is arrow::compute::WeekOptions for WEEK (NULL: {1, 0, 0} = the ISO week); ISO_WEEK is {1, 0, 0}, US_WEEK {0, 0, 0}.
+ * year_month_day() is {YEAR, MONTH, DAY} and iso_calendar() {ISO_YEAR, ISO_WEEK, ISO_DAY_OF_WEEK} in one call.  Nulls propagate:
+ * every output with a validity buffer receives the input's validity (an input with nulls needs one on every output); length 0 is
+ * PDX_OK.
+ *
+ * pdx_temporal_between: the number of `unit` boundaries crossed from a to b, floor(b, unit) - floor(a, unit) counted in units ->
+ * PDX_INT64, null where either side is null.  unit: any pdx_calendar_unit but MONTH (Arrow has no months_between): YEAR and QUARTER
+ * difference the calendar fields, WEEK counts Mondays (Arrow's default, which the reference uses).  Unequal lengths: PDX_INVALID
+ * "Array arguments must all be the same length".  A difference that overflows int64 (only NANOSECOND between instants more than
+ * 292 years apart can) wraps: outside the contract.
+ *
+ * Out of scope, refused by the facades with PDX_NOT_IMPLEMENTED naming the method: is_dst and anything that needs a time zone;
+ * strftime / strptime; day_time_interval_between, month_interval_between, month_day_nano_interval_between (no interval dtypes). */
+typedef enum pdx_temporal_component {
+  PDX_TC_YEAR = 0, PDX_TC_MONTH = 1, PDX_TC_DAY = 2, PDX_TC_DAY_OF_WEEK = 3, PDX_TC_DAY_OF_YEAR = 4, PDX_TC_HOUR = 5, PDX_TC_MINUTE = 6,
+  PDX_TC_SECOND = 7, PDX_TC_MILLISECOND = 8, PDX_TC_MICROSECOND = 9, PDX_TC_NANOSECOND = 10, PDX_TC_QUARTER = 11, PDX_TC_ISO_WEEK = 12,
+  PDX_TC_ISO_YEAR = 13, PDX_TC_ISO_DAY_OF_WEEK = 14, PDX_TC_US_WEEK = 15, PDX_TC_US_YEAR = 16, PDX_TC_WEEK = 17,
+  PDX_TC_IS_LEAP_YEAR = 18, PDX_TC_SUBSECOND = 19
+} pdx_temporal_component;
+typedef struct pdx_week_options {
+  int32_t week_starts_monday;
+  int32_t count_from_zero;
+  int32_t first_week_is_fully_in_year;
+} pdx_week_options;
+int pdx_temporal_components(const pdx_column* ts, const int* components, int nc, const pdx_week_options* week_opts, pdx_mut_column* outs,
+                            void* stream);
+int pdx_temporal_between(int unit, const pdx_column* a, const pdx_column* b, pdx_mut_column* out, void* stream);
 
 /* ---------------------------------------------------------------- index alignment (the callers' slow path)
  * Binary operators on Series with UNEQUAL indexes go through Series::broadcast (src/series.cpp:212-227):

@@ -30,7 +30,10 @@ AGG_VARIANCE, AGG_STDDEV, AGG_PRODUCT, AGG_FIRST, AGG_LAST = range(5, 10)  # gro
 AGG_ALL, AGG_ANY, AGG_COUNT_DISTINCT = range(10, 13)  # group-by only: all / any need BOOL values
 ORIGIN_EPOCH, ORIGIN_START_DAY, ORIGIN_START, ORIGIN_END, ORIGIN_END_DAY, ORIGIN_CUSTOM = range(6)
 (UNIT_NANOSECOND, UNIT_MICROSECOND, UNIT_MILLISECOND, UNIT_SECOND, UNIT_MINUTE, UNIT_HOUR, UNIT_DAY, UNIT_WEEK, UNIT_MONTH,
- UNIT_QUARTER) = range(10)  # pdx_calendar_unit
+ UNIT_QUARTER, UNIT_YEAR) = range(11)  # pdx_calendar_unit (YEAR: pdx_temporal_between only)
+ROUND_FLOOR, ROUND_CEIL, ROUND_NEAREST = range(3)  # pdx_round_mode
+(TC_YEAR, TC_MONTH, TC_DAY, TC_DAY_OF_WEEK, TC_DAY_OF_YEAR, TC_HOUR, TC_MINUTE, TC_SECOND, TC_MILLISECOND, TC_MICROSECOND, TC_NANOSECOND,
+ TC_QUARTER, TC_ISO_WEEK, TC_ISO_YEAR, TC_ISO_DAY_OF_WEEK, TC_US_WEEK, TC_US_YEAR, TC_WEEK, TC_IS_LEAP_YEAR, TC_SUBSECOND) = range(20)  # pdx_temporal_component
 ORIGIN_SHARD = 0x100  # OR-ed into the origin type for a row-range shard of a longer axis (include/pdx/abi.h)
 
 
@@ -50,6 +53,10 @@ class _ScalarValue(C.Union):
 
 class PdxScalar(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("is_valid", C.c_int32), ("v", _ScalarValue), ("count", C.c_int64)]
+
+
+class PdxWeekOptions(C.Structure):
+    _fields_ = [("week_starts_monday", C.c_int32), ("count_from_zero", C.c_int32), ("first_week_is_fully_in_year", C.c_int32)]
 
 
 class PdxError(RuntimeError):
@@ -127,6 +134,8 @@ ABI_SYMBOLS = {
     "pdx_resample_grid": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pdx_resample_row_labels": (C.c_int, [_P, _P, _P]),
     "pdx_round_temporal": (C.c_int, [C.c_int, _COL, C.c_int64, C.c_int, C.c_int, C.c_int, _MUT, _P]),
+    "pdx_temporal_components": (C.c_int, [_COL, C.POINTER(C.c_int), C.c_int, C.POINTER(PdxWeekOptions), _MUT, _P]),
+    "pdx_temporal_between": (C.c_int, [C.c_int, _COL, _COL, _MUT, _P]),
     "pdx_downsample_create": (C.c_int, [_COL, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.POINTER(_P)]),
     "pdx_concat": (C.c_int, [_COL, C.c_int, _MUT, _P]),
     "pdx_ipc_open": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),

@@ -416,6 +416,118 @@ class Series:
     def resample(self, rule, closed_right=False, label_right=False, origin=L.ORIGIN_START_DAY, offset_ns=0, origin_custom_ns=0):
         return DataFrame({self.name or "0": self}, index=self.index).resample(rule, closed_right, label_right, origin, offset_ns, origin_custom_ns)
 
+    @property
+    def dt(self):
+        """Series::dt() (src/series.cpp:461-466): a timestamp Series as it is, anything else through Arrow's cast to timestamp[ns] --
+        int64 values are reinterpreted as nanoseconds, every other type has no such cast."""
+        if self.col.dtype == L.TIMESTAMP_NS:
+            return DateTimeLike(self.col, self.index)
+        if self.col.dtype == L.INT64:
+            c = self.col
+            return DateTimeLike(Column(L.TIMESTAMP_NS, c.length, c.values, c.validity, c.offset, c.null_count), self.index)
+        name = {L.FLOAT64: "double", L.BOOL: "bool", L.UINT64: "uint64", L.INT32: "int32", L.FLOAT32: "float"}[self.col.dtype]
+        raise L.PdxError(L.NOT_IMPLEMENTED, f"Unsupported cast from {name} to timestamp using function cast_timestamp")
+
+
+_CALENDAR_UNITS = {"nanosecond": L.UNIT_NANOSECOND, "microsecond": L.UNIT_MICROSECOND, "millisecond": L.UNIT_MILLISECOND, "second": L.UNIT_SECOND,
+                   "minute": L.UNIT_MINUTE, "hour": L.UNIT_HOUR, "day": L.UNIT_DAY, "week": L.UNIT_WEEK, "month": L.UNIT_MONTH,
+                   "quarter": L.UNIT_QUARTER, "year": L.UNIT_YEAR}
+
+
+class DateTimeLike:
+    """pd::DateTimeLike (src/datetimelike.h; src/series.cpp:642-685, 1387-1487; src/dataframe.cpp:904-913): the Arrow temporal kernels
+    of a timestamp[ns] Series.  Every result keeps the Series' index.  `unit` is an L.UNIT_* code or Arrow's name ("day")."""
+
+    def __init__(self, col: Column, index=None):
+        self.col = col
+        self.index = index
+
+    def _series(self, col):
+        return Series(col, index=self.index, name="")
+
+    def _one(self, comp, week_options=None):
+        return self._series(K.temporal_components(self.col, [comp], week_options)[0])
+
+    def _frame(self, comps, names):
+        return DataFrame(dict(zip(names, K.temporal_components(self.col, comps))), index=self.index)
+
+    def _round(self, how, multiple, unit, week_starts_monday, ceil_is_strictly_greater, calendar_based_origin):
+        if ceil_is_strictly_greater and how != "floor":
+            raise L.PdxError(L.NOT_IMPLEMENTED, f"DateTimeLike.{how}: ceil_is_strictly_greater = true is not supported")
+        unit = _CALENDAR_UNITS[unit] if isinstance(unit, str) else int(unit)
+        return self._series(K.round_temporal(self.col, multiple, unit, how == "ceil", week_starts_monday, calendar_based_origin, nearest=how == "round"))
+
+    def ceil(self, multiple=1, unit=L.UNIT_DAY, week_starts_monday=True, ceil_is_strictly_greater=False, calendar_based_origin=False):
+        return self._round("ceil", multiple, unit, week_starts_monday, ceil_is_strictly_greater, calendar_based_origin)
+
+    def floor(self, multiple=1, unit=L.UNIT_DAY, week_starts_monday=True, ceil_is_strictly_greater=False, calendar_based_origin=False):
+        return self._round("floor", multiple, unit, week_starts_monday, ceil_is_strictly_greater, calendar_based_origin)
+
+    def round(self, multiple=1, unit=L.UNIT_DAY, week_starts_monday=True, ceil_is_strictly_greater=False, calendar_based_origin=False):
+        return self._round("round", multiple, unit, week_starts_monday, ceil_is_strictly_greater, calendar_based_origin)
+
+    def day(self): return self._one(L.TC_DAY)
+    def day_of_week(self): return self._one(L.TC_DAY_OF_WEEK)  # no options at the reference's call site: Monday = 0
+    def day_of_year(self): return self._one(L.TC_DAY_OF_YEAR)
+    def hour(self): return self._one(L.TC_HOUR)
+    def iso_week(self): return self._one(L.TC_ISO_WEEK)
+    def iso_year(self): return self._one(L.TC_ISO_YEAR)
+    def is_leap_year(self): return self._one(L.TC_IS_LEAP_YEAR)
+    def microsecond(self): return self._one(L.TC_MICROSECOND)
+    def millisecond(self): return self._one(L.TC_MILLISECOND)
+    def minute(self): return self._one(L.TC_MINUTE)
+    def month(self): return self._one(L.TC_MONTH)
+    def nanosecond(self): return self._one(L.TC_NANOSECOND)
+    def quarter(self): return self._one(L.TC_QUARTER)
+    def second(self): return self._one(L.TC_SECOND)
+    def subsecond(self): return self._one(L.TC_SUBSECOND)
+    def us_week(self): return self._one(L.TC_US_WEEK)
+    def us_year(self): return self._one(L.TC_US_YEAR)
+    def year(self): return self._one(L.TC_YEAR)
+
+    def week(self, week_starts_monday=True, count_from_zero=False, first_week_is_fully_in_year=False):
+        return self._one(L.TC_WEEK, (week_starts_monday, count_from_zero, first_week_is_fully_in_year))
+
+    def iso_calendar(self):
+        return self._frame([L.TC_ISO_YEAR, L.TC_ISO_WEEK, L.TC_ISO_DAY_OF_WEEK], ["iso_year", "iso_week", "iso_day_of_week"])
+
+    def year_month_day(self):
+        """Arrow's year_month_day fields.  (The reference's own body calls ISOCalendar and renames its fields, src/dataframe.cpp:910-913;
+        its commented-out test expects 2022 / 1 / 1, i.e. the civil date, which is what this returns.)"""
+        return self._frame([L.TC_YEAR, L.TC_MONTH, L.TC_DAY], ["year", "month", "day"])
+
+    def components(self, names, week_options=None):
+        """Any 1 .. 8 components by name from one read of the column -> DataFrame (a multi-column group-by key in one pass)."""
+        return DataFrame(dict(zip(names, K.temporal_components(self.col, [getattr(L, "TC_" + n.upper()) for n in names], week_options))), index=self.index)
+
+    def _between(self, unit, other):
+        o = other.col if isinstance(other, (Series, DateTimeLike)) else other
+        if o.dtype == L.INT64:  # (an int64 operand is cast like dt() casts it)
+            o = Column(L.TIMESTAMP_NS, o.length, o.values, o.validity, o.offset, o.null_count)
+        return self._series(K.temporal_between(unit, self.col, o))
+
+    def years_between(self, other): return self._between(L.UNIT_YEAR, other)
+    def quarters_between(self, other): return self._between(L.UNIT_QUARTER, other)
+    def weeks_between(self, other): return self._between(L.UNIT_WEEK, other)
+    def days_between(self, other): return self._between(L.UNIT_DAY, other)
+    def hours_between(self, other): return self._between(L.UNIT_HOUR, other)
+    def minutes_between(self, other): return self._between(L.UNIT_MINUTE, other)
+    def seconds_between(self, other): return self._between(L.UNIT_SECOND, other)
+    def milliseconds_between(self, other): return self._between(L.UNIT_MILLISECOND, other)
+    def microseconds_between(self, other): return self._between(L.UNIT_MICROSECOND, other)
+    def nanoseconds_between(self, other): return self._between(L.UNIT_NANOSECOND, other)
+
+    # out of scope (include/pdx/abi.h): time zones, string formatting, interval dtypes
+    def _refuse(self, method, why):
+        raise L.PdxError(L.NOT_IMPLEMENTED, f"DateTimeLike.{method}: {why}")
+
+    def is_dst(self): self._refuse("is_dst", "timestamps carry no time zone")
+    def strftime(self, *a, **k): self._refuse("strftime", "there are no string columns")
+    def strptime(self, *a, **k): self._refuse("strptime", "there are no string columns")
+    def day_time_interval_between(self, other): self._refuse("day_time_interval_between", "there are no interval dtypes")
+    def month_interval_between(self, other): self._refuse("month_interval_between", "there are no interval dtypes")
+    def month_day_nano_interval_between(self, other): self._refuse("month_day_nano_interval_between", "there are no interval dtypes")
+
 
 class DataFrame:
     def __init__(self, columns, index=None):

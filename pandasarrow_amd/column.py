@@ -423,13 +423,41 @@ def concat(parts) -> Column:
 
 
 # ---------------------------------------------------------------- temporal rounding (DataFrame::downsample)
-def round_temporal(ts: Column, multiple, unit, ceil=False, week_starts_monday=True, calendar_based_origin=False) -> Column:
-    """floor_temporal / ceil_temporal of a timestamp[ns] column (pdx_round_temporal)."""
+def round_temporal(ts: Column, multiple, unit, ceil=False, week_starts_monday=True, calendar_based_origin=False, nearest=False) -> Column:
+    """floor_temporal / ceil_temporal / round_temporal (nearest) of a timestamp[ns] column (pdx_round_temporal)."""
     out = Column.empty(L.TIMESTAMP_NS, ts.length, with_validity=ts.has_nulls())
     m = out.mut()
     ct = ts.c()
-    L.check(L.load().pdx_round_temporal(int(bool(ceil)), C.byref(ct), int(multiple), int(unit), int(bool(week_starts_monday)),
+    how = L.ROUND_NEAREST if nearest else int(bool(ceil))
+    L.check(L.load().pdx_round_temporal(how, C.byref(ct), int(multiple), int(unit), int(bool(week_starts_monday)),
                                         int(bool(calendar_based_origin)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def temporal_component_dtype(comp):
+    return L.BOOL if comp == L.TC_IS_LEAP_YEAR else L.FLOAT64 if comp == L.TC_SUBSECOND else L.INT64
+
+
+def temporal_components(ts: Column, comps, week_options=None):
+    """Calendar components of a timestamp[ns] column, all from ONE read of it (pdx_temporal_components): 1 .. 8 pdx_temporal_component
+    codes -> list of Columns (int64; bool for is_leap_year; float64 for subsecond).  week_options: (week_starts_monday, count_from_zero,
+    first_week_is_fully_in_year) for TC_WEEK."""
+    comps = [int(c) for c in comps]
+    outs = [Column.empty(temporal_component_dtype(c), ts.length, with_validity=ts.has_nulls()) for c in comps]
+    marr = _mut_array(outs) if outs else None
+    carr = (C.c_int * max(len(comps), 1))(*comps)
+    wo = None if week_options is None else C.byref(L.PdxWeekOptions(*[int(bool(x)) for x in week_options]))
+    ct = ts.c()
+    L.check(L.load().pdx_temporal_components(C.byref(ct), carr, len(comps), wo, marr, _stream()))
+    return [o._adopt(marr[i]) for i, o in enumerate(outs)]
+
+
+def temporal_between(unit, a: Column, b: Column) -> Column:
+    """<unit>s_between(a, b): unit boundaries crossed from a to b, int64 (pdx_temporal_between)."""
+    out = Column.empty(L.INT64, a.length, with_validity=a.has_nulls() or b.has_nulls())
+    m = out.mut()
+    ca, cb = a.c(), b.c()
+    L.check(L.load().pdx_temporal_between(int(unit), C.byref(ca), C.byref(cb), C.byref(m), _stream()))
     return out._adopt(m)
 
 

@@ -197,6 +197,11 @@ enum class Interpolation { LINEAR = PDX_INTERP_LINEAR, LOWER = PDX_INTERP_LOWER,
 class DataFrame;
 struct GroupBy;
 struct Resampler;
+struct DateTimeLike;
+// arrow::compute::CalendarUnit (pdx_calendar_unit) for DateTimeLike::floor / ceil / round
+enum class CalendarUnit { NANOSECOND = PDX_UNIT_NANOSECOND, MICROSECOND = PDX_UNIT_MICROSECOND, MILLISECOND = PDX_UNIT_MILLISECOND,
+                          SECOND = PDX_UNIT_SECOND, MINUTE = PDX_UNIT_MINUTE, HOUR = PDX_UNIT_HOUR, DAY = PDX_UNIT_DAY, WEEK = PDX_UNIT_WEEK,
+                          MONTH = PDX_UNIT_MONTH, QUARTER = PDX_UNIT_QUARTER, YEAR = PDX_UNIT_YEAR };
 
 // ---------------------------------------------------------------- pd::Series
 class Series {
@@ -346,6 +351,8 @@ class Series {
     return Series(run_shift(m_array, periods, fillValue), m_index, m_name);
   }
   Series pow(double x) const { return wrap(run_power(m_array, x)); }
+  // Series::dt() (src/series.cpp:461-466): a timestamp Series as it is, anything else through Arrow's cast to timestamp[ns]
+  DateTimeLike dt() const;
 
   // ---- comparisons (src/series.cpp:247-257) and logical (259-261, 319)
   Series compare(int op, const Series& o) const {
@@ -613,6 +620,114 @@ class Series {
     return cols;
   }
 };
+// ---------------------------------------------------------------- pd::DateTimeLike (src/datetimelike.h; src/series.cpp:642-685, 1387-1487)
+// The Arrow temporal kernels of a timestamp[ns] Series: one pdx_temporal_components / pdx_temporal_between / pdx_round_temporal call
+// each; every result keeps the Series' index.  Out of scope (include/pdx/abi.h): is_dst, the three *_interval_between and
+// ceil_is_strictly_greater = true -- they throw "NotImplemented: DateTimeLike::<method>: ..." (the text of Arrow's Status::NotImplemented,
+// as Series::dt() does for a type without a cast to timestamp).  components() is an addition to the reference's surface: the fused call.
+struct DateTimeLike : public Series {
+  Series ceil(int multiple = 1, CalendarUnit unit = CalendarUnit::DAY, bool week_starts_monday = true, bool ceil_is_strictly_greater = false,
+              bool calendar_based_origin = false) const {
+    return rounded(PDX_ROUND_CEIL, "ceil", multiple, unit, week_starts_monday, ceil_is_strictly_greater, calendar_based_origin);
+  }
+  Series floor(int multiple = 1, CalendarUnit unit = CalendarUnit::DAY, bool week_starts_monday = true, bool ceil_is_strictly_greater = false,
+               bool calendar_based_origin = false) const {
+    return rounded(PDX_ROUND_FLOOR, "floor", multiple, unit, week_starts_monday, false, calendar_based_origin);
+  }
+  Series round(int multiple = 1, CalendarUnit unit = CalendarUnit::DAY, bool week_starts_monday = true, bool ceil_is_strictly_greater = false,
+               bool calendar_based_origin = false) const {
+    return rounded(PDX_ROUND_NEAREST, "round", multiple, unit, week_starts_monday, ceil_is_strictly_greater, calendar_based_origin);
+  }
+
+  Series day() const { return component(PDX_TC_DAY); }
+  Series day_of_week() const { return component(PDX_TC_DAY_OF_WEEK); }  // no options at the reference's call site: Monday = 0
+  Series day_of_year() const { return component(PDX_TC_DAY_OF_YEAR); }
+  Series hour() const { return component(PDX_TC_HOUR); }
+  Series is_dst() const { throw std::runtime_error("NotImplemented: DateTimeLike::is_dst: timestamps carry no time zone"); }
+  Series iso_week() const { return component(PDX_TC_ISO_WEEK); }
+  Series iso_year() const { return component(PDX_TC_ISO_YEAR); }
+  DataFrame iso_calendar() const;
+  Series is_leap_year() const { return component(PDX_TC_IS_LEAP_YEAR); }
+  Series microsecond() const { return component(PDX_TC_MICROSECOND); }
+  Series millisecond() const { return component(PDX_TC_MILLISECOND); }
+  Series minute() const { return component(PDX_TC_MINUTE); }
+  Series month() const { return component(PDX_TC_MONTH); }
+  Series nanosecond() const { return component(PDX_TC_NANOSECOND); }
+  Series quarter() const { return component(PDX_TC_QUARTER); }
+  Series second() const { return component(PDX_TC_SECOND); }
+  Series subsecond() const { return component(PDX_TC_SUBSECOND); }
+  Series us_week() const { return component(PDX_TC_US_WEEK); }
+  Series us_year() const { return component(PDX_TC_US_YEAR); }
+  Series week(bool week_starts_monday = true, bool count_from_zero = false, bool first_week_is_fully_in_year = false) const {
+    const pdx_week_options w{week_starts_monday, count_from_zero, first_week_is_fully_in_year};
+    return Series(components({PDX_TC_WEEK}, &w)[0], m_index, "");
+  }
+  Series year() const { return component(PDX_TC_YEAR); }
+  // Arrow's year_month_day fields (the reference's body calls ISOCalendar and renames its fields, src/dataframe.cpp:910-913; its
+  // commented-out test expects the civil date 2022 / 1 / 1, which is what this returns)
+  DataFrame year_month_day() const;
+
+  Series day_time_interval_between(const Series&) const { throw std::runtime_error("NotImplemented: DateTimeLike::day_time_interval_between: there are no interval dtypes"); }
+  Series days_between(const Series& other) const { return between(PDX_UNIT_DAY, other); }
+  Series hours_between(const Series& other) const { return between(PDX_UNIT_HOUR, other); }
+  Series microseconds_between(const Series& other) const { return between(PDX_UNIT_MICROSECOND, other); }
+  Series milliseconds_between(const Series& other) const { return between(PDX_UNIT_MILLISECOND, other); }
+  Series minutes_between(const Series& other) const { return between(PDX_UNIT_MINUTE, other); }
+  Series month_day_nano_interval_between(const Series&) const { throw std::runtime_error("NotImplemented: DateTimeLike::month_day_nano_interval_between: there are no interval dtypes"); }
+  Series month_interval_between(const Series&) const { throw std::runtime_error("NotImplemented: DateTimeLike::month_interval_between: there are no interval dtypes"); }
+  Series nanoseconds_between(const Series& other) const { return between(PDX_UNIT_NANOSECOND, other); }
+  Series quarters_between(const Series& other) const { return between(PDX_UNIT_QUARTER, other); }
+  Series seconds_between(const Series& other) const { return between(PDX_UNIT_SECOND, other); }
+  Series weeks_between(const Series& other) const { return between(PDX_UNIT_WEEK, other); }
+  Series years_between(const Series& other) const { return between(PDX_UNIT_YEAR, other); }
+
+  // 1 .. 8 pdx_temporal_component codes from ONE read of the column
+  std::vector<Array> components(const std::vector<int>& comps, const pdx_week_options* w = nullptr) const {
+    std::vector<Array> outs;
+    std::vector<pdx_mut_column> mo;
+    for (int c : comps) outs.push_back(Array::Empty(c == PDX_TC_IS_LEAP_YEAR ? PDX_BOOL : c == PDX_TC_SUBSECOND ? PDX_FLOAT64 : PDX_INT64, size(), m_array.has_nulls()));
+    for (auto& o : outs) mo.push_back(o.mut());
+    auto ct = m_array.c();
+    ThrowOnFailure(pdx_temporal_components(&ct, comps.data(), (int)comps.size(), w, mo.data(), nullptr));
+    for (size_t i = 0; i < outs.size(); ++i) outs[i].null_count = mo[i].null_count;
+    return outs;
+  }
+
+ private:
+  friend class Series;
+  DateTimeLike(const Array& array, std::optional<Array> index) : Series(array, std::move(index), "", true) {}
+  Series component(int c) const { return Series(components({c})[0], m_index, ""); }
+  Series between(int unit, const Series& other) const {
+    Array b = other.m_array;
+    if (b.dtype == PDX_INT64) b.dtype = PDX_TIMESTAMP_NS;  // (an int64 operand is cast like dt() casts it)
+    Array out = Array::Empty(PDX_INT64, size(), m_array.has_nulls() || b.has_nulls());
+    auto ca = m_array.c(), cb = b.c();
+    auto m = out.mut();
+    ThrowOnFailure(pdx_temporal_between(unit, &ca, &cb, &m, nullptr));
+    out.null_count = m.null_count;
+    return Series(std::move(out), m_index, "");
+  }
+  Series rounded(int how, const char* name, int multiple, CalendarUnit unit, bool week_starts_monday, bool strictly_greater, bool calendar_based_origin) const {
+    if (strictly_greater) throw std::runtime_error(std::string("NotImplemented: DateTimeLike::") + name + ": ceil_is_strictly_greater = true is not supported");
+    Array out = Array::Empty(PDX_TIMESTAMP_NS, size(), m_array.has_nulls());
+    auto ct = m_array.c();
+    auto m = out.mut();
+    ThrowOnFailure(pdx_round_temporal(how, &ct, multiple, (int)unit, week_starts_monday, calendar_based_origin, &m, nullptr));
+    out.null_count = m.null_count;
+    return Series(std::move(out), m_index, "");
+  }
+};
+inline DateTimeLike Series::dt() const {
+  if (m_array.dtype == PDX_TIMESTAMP_NS) return DateTimeLike(m_array, m_index);
+  if (m_array.dtype == PDX_INT64) {  // Arrow's cast int64 -> timestamp[ns] reinterprets the values
+    Array a = m_array;
+    a.dtype = PDX_TIMESTAMP_NS;
+    return DateTimeLike(a, m_index);
+  }
+  static const char* names[] = {"int64", "double", "bool", "uint64", "timestamp", "int32", "float"};
+  throw std::runtime_error(std::string("NotImplemented: Unsupported cast from ") + names[m_array.dtype] + " to timestamp using function cast_timestamp");
+}
+
 // BINARY_OPERATOR_2 (src/scalar.cpp:12-56): Scalar op Series = CallFunction(name, {scalar, s.array()}) with the Series' index --
 // the scalar stays the LEFT operand (2 - s, 2 / s), pdx_binary / pdx_compare with PDX_SCALAR_LHS
 inline Series scalar_lhs(int op, const Scalar& a, const Series& b, bool cmp) {
@@ -1283,6 +1398,13 @@ inline Resampler resample(const Series& s, int64_t freq_ns, bool closed_right = 
   return resample(DataFrame({s.name().empty() ? "0" : s.name()}, {s.m_array}, s.m_index), freq_ns, closed_right, label_right);
 }
 // getCalendarUnit (src/core.cpp:135-172): first letter of the rule's unit
+inline DataFrame DateTimeLike::iso_calendar() const {
+  return DataFrame({"iso_year", "iso_week", "iso_day_of_week"}, components({PDX_TC_ISO_YEAR, PDX_TC_ISO_WEEK, PDX_TC_ISO_DAY_OF_WEEK}), m_index);
+}
+inline DataFrame DateTimeLike::year_month_day() const {
+  return DataFrame({"year", "month", "day"}, components({PDX_TC_YEAR, PDX_TC_MONTH, PDX_TC_DAY}), m_index);
+}
+
 inline int calendar_unit(char c) {
   switch (c) {
     case 'n': return PDX_UNIT_NANOSECOND;

@@ -1,6 +1,7 @@
-// temporal_round.hpp -- Arrow's floor_temporal / ceil_temporal on one int64 nanosecond timestamp, as device functions shared by
-// pdx_round_temporal (temporal.hip: the rounded column) and pdx_downsample_create (groupby.hip: runs of equal rounded labels without
-// materialising the column).  Semantics and their pinning: see temporal.hip.
+// temporal_round.hpp -- Arrow's floor_temporal / ceil_temporal / round_temporal on one int64 nanosecond timestamp, as device functions
+// shared by pdx_round_temporal (temporal.hip: the rounded column) and pdx_downsample_create (groupby.hip: runs of equal rounded labels
+// without materialising the column), and the calendar fields behind pdx_temporal_components / pdx_temporal_between.  Semantics and their
+// pinning: see temporal.hip.
 #pragma once
 #include "pdx_common.hpp"
 
@@ -117,10 +118,9 @@ __device__ __forceinline__ long long floor_one(long long t, const RoundParams& q
   }
 }
 
-template <int MODE, bool CEIL>
-__device__ __forceinline__ long long round_one(long long t, const RoundParams& q) {
-  const long long f = floor_one<MODE>(t, q);
-  if constexpr (!CEIL) return f;
+// the ceil that belongs to the floor f of t
+template <int MODE>
+__device__ __forceinline__ long long ceil_of_floor(long long t, long long f, const RoundParams& q) {
   if constexpr (MODE <= 6) return f >= t ? f : f + q.p;
   long long y;
   int m;
@@ -128,6 +128,21 @@ __device__ __forceinline__ long long round_one(long long t, const RoundParams& q
   const long long tm = y * 12 + m - 1 + q.mult;
   const long long yy = fdiv(tm, 12);
   return days_from_civil(yy, (int)(tm - yy * 12) + 1, 1) * kNsPerDay;
+}
+
+template <int MODE, bool CEIL>
+__device__ __forceinline__ long long round_one(long long t, const RoundParams& q) {
+  const long long f = floor_one<MODE>(t, q);
+  if constexpr (!CEIL) return f;
+  return ceil_of_floor<MODE>(t, f, q);
+}
+
+// round_temporal: of the floor f and the ceil c the nearer one, the ceil on a tie (t - f >= c - t)
+template <int MODE>
+__device__ __forceinline__ long long nearest_one(long long t, const RoundParams& q) {
+  const long long f = floor_one<MODE>(t, q);
+  const long long c = ceil_of_floor<MODE>(t, f, q);
+  return (t - f >= c - t) ? c : f;
 }
 
 // RoundTemporalOptions -> kernel parameters and MODE; returns a PDX_* code (message through fail()).
@@ -163,6 +178,108 @@ inline int make_round_params(int64_t multiple, int unit, int week_starts_monday,
   *out = q;
   *mode_out = mode;
   return PDX_OK;
+}
+
+// ---------------------------------------------------------------- calendar fields of one timestamp (pdx_temporal_components / _between)
+// Every int64 nanosecond timestamp lies within +-106752 days of the epoch (1677-09-21 .. 2262-04-11), so all day arithmetic fits 32 bits
+// and the shifted day number below is positive: unsigned divisions by constants, no sign fix-ups.
+constexpr unsigned kTfTod = 1, kTfCivil = 2, kTfIso = 4, kTfUs = 8, kTfWeek = 16;  // field families (what a component needs)
+
+struct WeekOpts {  // arrow::compute::WeekOptions
+  int week_starts_monday, count_from_zero, first_week_is_fully_in_year;
+};
+
+struct TemporalFields {
+  int days;                            // floor(t / 1 day)
+  int dow;                             // 0 = Monday .. 6 = Sunday
+  int y, m, d, doy;                    // civil date, doy: 1 = 1 January
+  bool leap;
+  int hour, minute, second, ms, us, ns;
+  unsigned subns;                      // nanoseconds since the last whole second
+  int iso_y, iso_w, us_y, us_w, week;
+};
+
+__device__ __forceinline__ int floor_days(long long t) { return (int)fdiv_c(t, kNsPerDay, 1.0 / (double)kNsPerDay); }
+__device__ __forceinline__ bool leap_year(int y) { return (y % 4 == 0) && (y % 100 != 0 || y % 400 == 0); }
+__device__ __forceinline__ int weekday_sun0(int z) { return (int)((unsigned)(z + 4 + 7 * 20000) % 7u); }  // 1970-01-01 was a Thursday
+
+// civil_from_days with the day of the month, the day of the year and the leap flag (same algorithm, 32-bit, z + 719468 > 0)
+__device__ __forceinline__ void civil_fields(int z, int* y, int* m, int* d, int* doy_jan, bool* leap) {
+  const unsigned zz = (unsigned)(z + 719468);
+  const unsigned era = zz / 146097u;
+  const unsigned doe = zz - era * 146097u;
+  const unsigned yoe = (doe - doe / 1460u + doe / 36524u - doe / 146096u) / 365u;
+  const unsigned doy = doe - (365u * yoe + yoe / 4u - yoe / 100u);  // 0 = 1 March
+  const unsigned mp = (5u * doy + 2u) / 153u;
+  *d = (int)(doy - (153u * mp + 2u) / 5u + 1u);
+  *m = (int)(mp < 10u ? mp + 3u : mp - 9u);
+  *y = (int)(yoe + era * 400u) + (*m <= 2);
+  *leap = leap_year(*y);
+  *doy_jan = *m > 2 ? (int)doy + 60 + (int)*leap : (int)doy - 305;
+}
+
+// Arrow's Week / ISOWeek / USWeek / ISOYear / USYear (scalar_temporal_unary.cc) on day numbers.  The year is that of z + 3 days (the
+// week's middle day) or of z itself (first_week_is_fully_in_year or count_from_zero); week 1 starts on the first Monday / Sunday of that year, or four days
+// after the last Thursday / Wednesday of the December before; a day before that start belongs to the year before unless count_from_zero,
+// where it is week 0.
+__device__ __forceinline__ int week_start(int jan1, bool monday, bool full) {
+  if (full) return jan1 + (int)((unsigned)((monday ? 1 : 0) - weekday_sun0(jan1) + 7) % 7u);
+  const int dec31 = jan1 - 1;
+  return dec31 - (int)((unsigned)(weekday_sun0(dec31) - (monday ? 4 : 3) + 7) % 7u) + 4;
+}
+__device__ __forceinline__ void week_of(int z, bool monday, bool from_zero, bool full, int* year, int* week) {
+  const int zo = z + (full || from_zero ? 0 : 3);
+  int y, m, d, doy;
+  bool leap;
+  civil_fields(zo, &y, &m, &d, &doy, &leap);
+  int jan1 = zo - (doy - 1);
+  int start = week_start(jan1, monday, full);
+  if (!from_zero && z < start) {
+    --y;
+    jan1 -= 365 + (int)leap_year(y);
+    start = week_start(jan1, monday, full);
+  }
+  *year = y;
+  *week = (z - start + 7) / 7;  // floor((z - start) / 7) + 1: z - start >= -6
+}
+
+template <unsigned FAM>
+__device__ __forceinline__ TemporalFields temporal_fields(long long t, const WeekOpts& w) {
+  TemporalFields f{};
+  f.days = floor_days(t);
+  f.dow = (int)((unsigned)(f.days + 3 + 7 * 20000) % 7u);
+  if constexpr (FAM & kTfTod) {  // one floor division (above), then remainders of a 47-bit and a 30-bit unsigned number
+    // (unsigned: days * 1 day lies below INT64_MIN for the first, partial day of the range; the difference is in [0, 1 day) modulo 2^64)
+    const unsigned long long tod = (unsigned long long)t - (unsigned long long)(long long)f.days * (unsigned long long)kNsPerDay;
+    const unsigned secs = (unsigned)(tod / 1000000000ull);
+    f.subns = (unsigned)(tod - (unsigned long long)secs * 1000000000ull);
+    f.hour = (int)(secs / 3600u);
+    f.minute = (int)(secs / 60u % 60u);
+    f.second = (int)(secs % 60u);
+    f.ms = (int)(f.subns / 1000000u);
+    f.us = (int)(f.subns / 1000u % 1000u);
+    f.ns = (int)(f.subns % 1000u);
+  }
+  if constexpr (FAM & kTfCivil) civil_fields(f.days, &f.y, &f.m, &f.d, &f.doy, &f.leap);
+  if constexpr (FAM & kTfIso) week_of(f.days, true, false, false, &f.iso_y, &f.iso_w);
+  if constexpr (FAM & kTfUs) week_of(f.days, false, false, false, &f.us_y, &f.us_w);
+  if constexpr (FAM & kTfWeek) {
+    int y;
+    week_of(f.days, w.week_starts_monday != 0, w.count_from_zero != 0, w.first_week_is_fully_in_year != 0, &y, &f.week);
+  }
+  return f;
+}
+
+constexpr unsigned temporal_family(int c) {
+  switch (c) {
+    case PDX_TC_YEAR: case PDX_TC_MONTH: case PDX_TC_DAY: case PDX_TC_DAY_OF_YEAR: case PDX_TC_QUARTER: case PDX_TC_IS_LEAP_YEAR: return kTfCivil;
+    case PDX_TC_HOUR: case PDX_TC_MINUTE: case PDX_TC_SECOND: case PDX_TC_MILLISECOND: case PDX_TC_MICROSECOND: case PDX_TC_NANOSECOND:
+    case PDX_TC_SUBSECOND: return kTfTod;
+    case PDX_TC_ISO_WEEK: case PDX_TC_ISO_YEAR: return kTfIso;
+    case PDX_TC_US_WEEK: case PDX_TC_US_YEAR: return kTfUs;
+    case PDX_TC_WEEK: return kTfWeek;
+    default: return 0;  // DAY_OF_WEEK, ISO_DAY_OF_WEEK: the day number alone
+  }
 }
 
 }  // namespace pdx

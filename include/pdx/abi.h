@@ -57,7 +57,7 @@ typedef enum pdx_dtype {
   PDX_UINT64 = 3,
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
-   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift and pdx_quantile; every
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile and pdx_sort_indices; every
    * other entry point returns
    * PDX_NOT_IMPLEMENTED naming the dtype.  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
    * widened (exactly) in v.f64. */
@@ -548,6 +548,27 @@ int pdx_reindex_indices(const pdx_column* old_index, const pdx_column* new_index
  * nulls behind the NaNs in BOTH orders.  col: int64 / uint64 / float64 / timestamp[ns], <= 2^31-1 rows; out_indices: PDX_UINT64,
  * capacity col.length (the take indices; feed them to pdx_take). */
 int pdx_argsort(const pdx_column* col, int ascending, pdx_mut_column* out_indices, void* stream);
+
+/* DataFrame::argsort (src/dataframe.cpp:1073-1091): CallFunction("sort_indices", SortOptions{one SortKey per field}) -- a STABLE
+ * lexicographic sort by several columns.  Semantics pinned against Arrow 25.0.0 (default null placement): per key first the class,
+ * numbers < NaN < null in BOTH orders (descending reverses only the numbers), then the value (-0.0 == 0.0: such a tie goes on to the
+ * next key); rows that tie on every key keep their row order.
+ *   keys: 1 .. PDX_SORT_MAX_KEYS columns of equal length (<= 2^31-1 rows), int64 / uint64 / float64 / timestamp[ns] / int32 / float32
+ *   (bool: PDX_NOT_IMPLEMENTED), each with its own offset and validity; descending: nkeys flags, NULL = all ascending;
+ *   out_indices: PDX_UINT64, capacity >= the row count (the take indices; feed them to pdx_take).
+ * The keys are sorted as range-compressed composite keys: per key a value field of bit_length(max - min) bits and, only when the
+ * column has a NaN or null row, a 2-bit class field above it; the fields of all keys, last key least significant, are packed without
+ * splitting a field into rounds of at most 64 bits, each round one stable radix sort.  info (optional) reports what ran: rounds = the
+ * composite sorts (0 when every field has width 0: the result is 0 .. n-1), key_bits = the sum of all field widths, passes = the 8-bit
+ * radix passes issued. */
+#define PDX_SORT_MAX_KEYS 16
+typedef struct pdx_sort_info {
+  int32_t rounds;
+  int32_t key_bits;
+  int32_t passes;
+  int32_t reserved;
+} pdx_sort_info;
+int pdx_sort_indices(const pdx_column* keys, int nkeys, const int* descending, pdx_mut_column* out_indices, pdx_sort_info* info, void* stream);
 
 /* ---------------------------------------------------------------- concat (rows)
  * Replaces arrow::ConcatenateTables + CombineChunksToBatch at src/concat.cpp:152-154 for same-dtype parts

@@ -34,6 +34,7 @@ ORIGIN_EPOCH, ORIGIN_START_DAY, ORIGIN_START, ORIGIN_END, ORIGIN_END_DAY, ORIGIN
 ROUND_FLOOR, ROUND_CEIL, ROUND_NEAREST = range(3)  # pdx_round_mode
 (TC_YEAR, TC_MONTH, TC_DAY, TC_DAY_OF_WEEK, TC_DAY_OF_YEAR, TC_HOUR, TC_MINUTE, TC_SECOND, TC_MILLISECOND, TC_MICROSECOND, TC_NANOSECOND,
  TC_QUARTER, TC_ISO_WEEK, TC_ISO_YEAR, TC_ISO_DAY_OF_WEEK, TC_US_WEEK, TC_US_YEAR, TC_WEEK, TC_IS_LEAP_YEAR, TC_SUBSECOND) = range(20)  # pdx_temporal_component
+SORT_MAX_KEYS = 16  # PDX_SORT_MAX_KEYS
 ORIGIN_SHARD = 0x100  # OR-ed into the origin type for a row-range shard of a longer axis (include/pdx/abi.h)
 
 
@@ -57,6 +58,11 @@ class PdxScalar(C.Structure):
 
 class PdxWeekOptions(C.Structure):
     _fields_ = [("week_starts_monday", C.c_int32), ("count_from_zero", C.c_int32), ("first_week_is_fully_in_year", C.c_int32)]
+
+
+class PdxSortInfo(C.Structure):
+    """pdx_sort_info: what pdx_sort_indices ran (composite sorts, sum of the field widths, radix passes)."""
+    _fields_ = [("rounds", C.c_int32), ("key_bits", C.c_int32), ("passes", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PdxError(RuntimeError):
@@ -187,6 +193,7 @@ ABI_SYMBOLS = {
     "pdx_index_union": (C.c_int, [_COL, _COL, C.c_int, _MUT, _P]),
     "pdx_index_intersection": (C.c_int, [_COL, _COL, _MUT, _P]),
     "pdx_argsort": (C.c_int, [_COL, C.c_int, _MUT, _P]),
+    "pdx_sort_indices": (C.c_int, [_COL, C.c_int, C.POINTER(C.c_int), _MUT, C.POINTER(PdxSortInfo), _P]),
     "pdx_reindex_indices": (C.c_int, [_COL, _COL, _MUT, _P]),
 }
 

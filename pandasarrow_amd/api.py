@@ -731,6 +731,33 @@ class DataFrame:
         outs = K.take(self.cols + [ix], idx)
         return self._like(outs[:-1], index=None if ignore_index else outs[-1])
 
+    def _sort_keys(self, fields, ascending):
+        fields = [fields] if isinstance(fields, str) else list(fields)
+        orders = [bool(ascending)] * len(fields) if isinstance(ascending, (bool, np.bool_)) else [bool(a) for a in ascending]
+        if len(orders) != len(fields):
+            raise L.PdxError(L.INVALID, f"{len(fields)} sort fields but {len(orders)} sort orders")
+        for f in fields:
+            if f not in self.names:
+                raise L.PdxError(L.INVALID, f"{f} not in schema")
+        return [self.cols[self.names.index(f)] for f in fields], [not a for a in orders]
+
+    def argsort(self, fields, ascending=True):
+        """DataFrame::argsort (src/dataframe.cpp:1073-1091): CallFunction("sort_indices") with one SortKey per field -> the uint64 take
+        indices of the stable lexicographic sort (a plain Series, not an index Series).  `ascending`: one bool, or one per field."""
+        keys, desc = self._sort_keys(fields, ascending)
+        return Series(K.sort_indices(keys, desc))
+
+    def sort_values(self, by, ascending=True):
+        """The rows AND the index ordered by the columns `by` (the pandas meaning): one multi-key argsort, one take per 16 columns.  (The reference's
+        body, src/dataframe.cpp:1188-1208, sorts every named column on its own and drops the index, which tears the rows apart: not reproduced.)"""
+        keys, desc = self._sort_keys(by, ascending)
+        idx = K.sort_indices(keys, desc)
+        cols = self.cols + [_frame_index(self)]
+        outs = []
+        for at in range(0, len(cols), 16):  # pdx_take serves 16 columns per call
+            outs += K.take(cols[at:at + 16], idx)
+        return self._like(outs[:-1], index=outs[-1])
+
     def reindex(self, new_index, fill_value=None):
         """DataFrame::reindex / reindexAsync (src/dataframe.cpp:1139-1186, src/dataframe.h:403-406): every column at the LAST position
         of each new label; absent labels -> null or `fill_value`.  One take plan (pdx_reindex_indices) serves all columns."""

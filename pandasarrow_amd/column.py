@@ -489,6 +489,20 @@ def argsort(a: Column, ascending=True) -> Column:
     return out._adopt(m)
 
 
+def sort_indices(keys, descending=None, with_info=False):
+    """uint64 take indices of the stable lexicographic sort by several key columns (pdx_sort_indices: Arrow's sort_indices; per key numbers
+    < NaN < null in both orders).  descending: one flag per key (None: all ascending).  with_info: -> (indices, (rounds, key_bits, passes))."""
+    keys = list(keys)
+    n = keys[0].length if keys else 0
+    out = Column.empty(L.UINT64, n)
+    m = out.mut()
+    desc = None if descending is None else (C.c_int * max(len(keys), 1))(*[int(bool(d)) for d in descending])
+    info = L.PdxSortInfo()
+    L.check(L.load().pdx_sort_indices(_col_array(keys) if keys else None, len(keys), desc, C.byref(m), C.byref(info), _stream()))
+    out._adopt(m)
+    return (out, (info.rounds, info.key_bits, info.passes)) if with_info else out
+
+
 def reindex_indices(old_index: Column, new_index: Column) -> Column:
     """int64 take indices (LAST position of every new label in old_index, null where absent)."""
     out = Column.empty(L.INT64, new_index.length, with_validity=True)

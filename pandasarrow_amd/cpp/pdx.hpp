@@ -993,6 +993,42 @@ class DataFrame {
     if (ignore_index) r.m_index.reset();
     return r;
   }
+  // DataFrame::argsort (src/dataframe.cpp:1073-1091): CallFunction("sort_indices", SortOptions{one SortKey per field}) -> the uint64 take
+  // indices of the stable lexicographic sort (a plain Series: no index attached).  The second form takes one order per field.
+  Series argsort(const std::vector<std::string>& fields, const std::vector<bool>& ascending) const {
+    if (ascending.size() != fields.size()) throw std::runtime_error("one sort order per sort field expected");
+    std::vector<pdx_column> keys;
+    std::vector<int> desc;
+    for (size_t i = 0; i < fields.size(); ++i) {
+      bool found = false;
+      for (size_t c = 0; c < m_names.size() && !found; ++c)
+        if (m_names[c] == fields[i]) {
+          keys.push_back(m_columns[c].c());
+          found = true;
+        }
+      if (!found) throw std::runtime_error(fields[i] + " not in schema");
+      desc.push_back(ascending[i] ? 0 : 1);
+    }
+    Array idx = Array::Empty(PDX_UINT64, num_rows(), false);
+    auto mi = idx.mut();
+    ThrowOnFailure(pdx_sort_indices(keys.data(), (int)keys.size(), desc.data(), &mi, nullptr, nullptr));
+    return Series(idx);
+  }
+  Series argsort(const std::vector<std::string>& fields, bool ascending) const { return argsort(fields, std::vector<bool>(fields.size(), ascending)); }
+  // The rows AND the index ordered by the columns `by` (the pandas meaning): one multi-key argsort, one take per 16 columns.  (The reference's body,
+  // src/dataframe.cpp:1188-1208, sorts every named column on its own and drops the index, which tears the rows apart: not reproduced.)
+  DataFrame sort_values(const std::vector<std::string>& by, const std::vector<bool>& ascending) const {
+    const Series order = argsort(by, ascending);
+    const std::vector<Array> cols = columns_with_index();
+    std::vector<Array> outs;
+    for (size_t at = 0; at < cols.size(); at += 16) {  // pdx_take serves 16 columns per call
+      auto part = Series::run_take(std::vector<Array>(cols.begin() + (long)at, cols.begin() + (long)std::min(at + 16, cols.size())), order.m_array);
+      outs.insert(outs.end(), part.begin(), part.end());
+    }
+    if (m_index) return rebuild(outs);
+    return DataFrame(m_names, outs, order.m_array);  // the implicit range index taken by the sort indices is the sort indices (Series::sort)
+  }
+  DataFrame sort_values(const std::vector<std::string>& by, bool ascending = true) const { return sort_values(by, std::vector<bool>(by.size(), ascending)); }
 
   // ---- Arrow IPC (src/dataframe.cpp:726-791).  toBinary: schema + ONE record batch + custom metadata; every column is written
   // (the reference computes `columns` and then serialises m_array whole); `index`: the index as a last int64 column of that name.

@@ -137,17 +137,10 @@ __global__ void k_pay_rows_u32(const unsigned long long* __restrict__ pay, int64
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint32_t)pay[i];
 }
 // Sorts the n packed elements (lo0, pay0) by their 64-bit key; `varying` = key bits that differ somewhere.  *sorted points at the
-// payloads in key order (one of the ping-pong buffers).
-static int sort_packed64(uint32_t* lo0, unsigned long long* pay0, int64_t n, unsigned long long varying, Scratch& s, hipStream_t st,
-                         const unsigned long long** sorted) {
-  *sorted = pay0;
-  if (n <= 1 || varying == 0) return PDX_OK;
-  const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);
-  uint32_t* lo1 = s.get<uint32_t>((size_t)n);
-  unsigned long long* pay1 = s.get<unsigned long long>((size_t)n);
-  uint32_t* hist = s.get<uint32_t>((size_t)ntiles << 8);
-  uint32_t* chunk = s.get<uint32_t>((size_t)(nchunks + 1) << 8);
-  PDX_SCRATCH_CHECK(s);
+// payloads in key order (one of the ping-pong buffers).  This form works in buffers of the caller's: lo1 / pay1 hold n elements, hist
+// ntiles << 8 and chunk (nchunks + 1) << 8 counters; *passes (optional) grows by the radix passes issued.
+static int sort_packed64_in(uint32_t* lo0, unsigned long long* pay0, uint32_t* lo1, unsigned long long* pay1, uint32_t* hist, uint32_t* chunk, int64_t n,
+                            unsigned long long varying, hipStream_t st, const unsigned long long** sorted, int* passes) {
   const uint32_t* kin = lo0;
   const unsigned long long* vin = pay0;
   int last_lo = -1;
@@ -164,10 +157,23 @@ static int sort_packed64(uint32_t* lo0, unsigned long long* pay0, int64_t n, uns
     } else {
       PDX_TRY((radix_pass_payload_hi<8>(reinterpret_cast<const uint64_t*>(vin), reinterpret_cast<uint64_t*>(vout), n, 8 * (d - 4), hist, chunk, st)));
     }
+    if (passes) ++*passes;
     vin = vout;
   }
   *sorted = vin;
   return PDX_OK;
+}
+static int sort_packed64(uint32_t* lo0, unsigned long long* pay0, int64_t n, unsigned long long varying, Scratch& s, hipStream_t st,
+                         const unsigned long long** sorted) {
+  *sorted = pay0;
+  if (n <= 1 || varying == 0) return PDX_OK;
+  const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);
+  uint32_t* lo1 = s.get<uint32_t>((size_t)n);
+  unsigned long long* pay1 = s.get<unsigned long long>((size_t)n);
+  uint32_t* hist = s.get<uint32_t>((size_t)ntiles << 8);
+  uint32_t* chunk = s.get<uint32_t>((size_t)(nchunks + 1) << 8);
+  PDX_SCRATCH_CHECK(s);
+  return sort_packed64_in(lo0, pay0, lo1, pay1, hist, chunk, n, varying, st, sorted, nullptr);
 }
 // perm[i] = index of the i-th smallest label (labels ^ flip in unsigned order), stable
 static int argsort_labels64(const long long* labels, int64_t n, unsigned long long flip, uint32_t* perm, Scratch& s, hipStream_t st) {
@@ -224,6 +230,102 @@ struct IntersectEmit {
   long long* out;
   __device__ void operator()(int64_t pos, int64_t i) const { out[pos] = a[n_a - 1 - first_rows[G - 1 - i]]; }
 };
+
+// ---- multi-key sort (pdx_sort_indices): range-compressed composite keys.  Per key column the ascending sort_image minus the column's
+// minimum needs only bit_length(max - min) bits; a 2-bit class field (0 number, 1 NaN, 2 null) above it, present only where the column
+// has a NaN / null row, places those rows as Arrow's sort_indices does.  The fields of several keys concatenated are ONE 64-bit key of
+// sort_packed64; keys wider than a word sort as an LSD chain of such rounds, least significant fields first (stable passes: the chain
+// is the lexicographic order, full ties keep their row order).
+struct SortKeyStats {
+  unsigned long long min, max;    // of the ascending image over the rows of class 0 (~0 / 0 when there is none)
+  unsigned long long nans, nulls;
+};
+struct SortKeyDesc {  // one key column as a round reads it; wave-uniform (kernel argument)
+  const void* v;         // values + offset
+  const uint8_t* valid;  // bitmap or nullptr
+  long long off;         // bit offset into valid
+  unsigned long long base;  // value field = img - base (ascending: the minimum) or base - img (descending: the maximum)
+  int dtype, descending;
+  int vshift, vwidth;  // value field: position in the round's key, width (0: not in this round)
+  int cshift;          // class field position (-1: not in this round)
+  int pad;
+};
+struct SortKeyDescs {
+  SortKeyDesc k[PDX_SORT_MAX_KEYS];
+  int n;
+};
+// the ascending image and class of row `row`; 4-byte keys widen here: int32 sign-extends, float32 converts to double (exact: order, NaN and
+// the -0 rule carry over)
+__device__ __forceinline__ unsigned long long sort_key_image(const SortKeyDesc& d, int64_t row, bool need_value, int* cls) {
+  const bool is_null = d.valid && !bit_get(d.valid, d.off + row);
+  unsigned long long u = 0;
+  int dt = d.dtype;
+  if (need_value) {
+    if (dt == PDX_INT32) {
+      u = (unsigned long long)(long long)static_cast<const int32_t*>(d.v)[row];
+      dt = PDX_INT64;
+    } else if (dt == PDX_FLOAT32) {
+      u = (unsigned long long)__double_as_longlong((double)static_cast<const float*>(d.v)[row]);
+      dt = PDX_FLOAT64;
+    } else {
+      u = static_cast<const unsigned long long*>(d.v)[row];
+    }
+  } else {
+    dt = PDX_UINT64;  // only the class is wanted and only a null makes one here
+  }
+  return sort_image(u, is_null, dt, 0, cls);
+}
+// grid.y = key: every key column is read once; per wave one 64-bit atomic per statistic
+__global__ void k_sort_key_stats(const SortKeyDescs keys, int64_t n, SortKeyStats* __restrict__ stats) {
+  const SortKeyDesc& d = keys.k[blockIdx.y];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  unsigned long long mn = ~0ull, mx = 0ull, nans = 0, nulls = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    int c;
+    const unsigned long long u = sort_key_image(d, i, true, &c);
+    if (c == 0) {
+      mn = u < mn ? u : mn;
+      mx = u > mx ? u : mx;
+    }
+    nans += c == 1;
+    nulls += c == 2;
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    const unsigned long long omn = __shfl_xor(mn, s, 64), omx = __shfl_xor(mx, s, 64);
+    mn = omn < mn ? omn : mn;
+    mx = omx > mx ? omx : mx;
+    nans += __shfl_xor(nans, s, 64);
+    nulls += __shfl_xor(nulls, s, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    SortKeyStats* st = stats + blockIdx.y;
+    if (mn <= mx) {
+      atomicMin(&st->min, mn);
+      atomicMax(&st->max, mx);
+    }
+    if (nans) atomicAdd(&st->nans, nans);
+    if (nulls) atomicAdd(&st->nulls, nulls);
+  }
+}
+// one round: the (lo, pay) element of sort_packed64 at position i for the row at position i of the previous round's order (prev ==
+// nullptr: row i itself).  The loop over the fields is wave-uniform; a row that is no number has value field 0.
+__global__ void k_sort_compose(const SortKeyDescs keys, const unsigned long long* __restrict__ prev, int64_t n, uint32_t* __restrict__ lo,
+                               unsigned long long* __restrict__ pay) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const unsigned long long row = prev ? (prev[i] & 0xFFFFFFFFull) : (unsigned long long)i;
+    unsigned long long key = 0;
+    for (int f = 0; f < keys.n; ++f) {
+      const SortKeyDesc& d = keys.k[f];
+      int c;
+      const unsigned long long u = sort_key_image(d, (int64_t)row, d.vwidth > 0 || d.dtype == PDX_FLOAT64 || d.dtype == PDX_FLOAT32, &c);
+      if (d.vwidth > 0) key |= (c == 0 ? (d.descending ? d.base - u : u - d.base) : 0ull) << d.vshift;
+      if (d.cshift >= 0) key |= (unsigned long long)c << d.cshift;
+    }
+    lo[i] = (uint32_t)key;
+    pay[i] = (key & 0xFFFFFFFF00000000ull) | row;
+  }
+}
 
 }  // namespace pdx
 
@@ -333,6 +435,120 @@ int pdx_argsort(const pdx_column* col, int ascending, pdx_mut_column* out, void*
   PDX_LAUNCH_CHECK();
   if (out->validity) PDX_HIP(hipMemsetAsync(out->validity, 0xFF, (size_t)((n + 7) / 8), st));
   PDX_HIP(hipStreamSynchronize(st));
+  return PDX_OK;
+}
+
+int pdx_sort_indices(const pdx_column* keys, int nkeys, const int* descending, pdx_mut_column* out, pdx_sort_info* info, void* stream) {
+  if (info) *info = pdx_sort_info{0, 0, 0, 0};
+  if (nkeys < 1 || nkeys > PDX_SORT_MAX_KEYS) return fail(PDX_INVALID, "pdx_sort_indices: between 1 and " + std::to_string(PDX_SORT_MAX_KEYS) + " sort keys");
+  if (!keys) return fail(PDX_INVALID, "pdx_sort_indices: null keys");
+  if (!out) return fail(PDX_INVALID, "pdx_sort_indices: null output");
+  for (int k = 0; k < nkeys; ++k) {
+    const int dt = keys[k].dtype;
+    if (dt != PDX_INT64 && dt != PDX_UINT64 && dt != PDX_FLOAT64 && dt != PDX_TIMESTAMP_NS && dt != PDX_INT32 && dt != PDX_FLOAT32)
+      return fail(PDX_NOT_IMPLEMENTED, "pdx_sort_indices: int64 / uint64 / float64 / timestamp[ns] / int32 / float32 keys only");
+    if (keys[k].length < 0 || keys[k].offset < 0) return fail(PDX_INVALID, "pdx_sort_indices: negative length/offset");
+    if (keys[k].length != keys[0].length) return fail(PDX_INVALID, "pdx_sort_indices: all keys must have the same length");
+  }
+  const int64_t n = keys[0].length;
+  if (out->dtype != PDX_UINT64) return fail(PDX_INVALID, "pdx_sort_indices: the indices are uint64");
+  if (out->length < n) return fail(PDX_INVALID, "pdx_sort_indices: output too small");
+  if (n > 0x7FFFFFFFll) return fail(PDX_NOT_IMPLEMENTED, "pdx_sort_indices: more than 2^31-1 rows per call is not supported yet");
+  for (int k = 0; k < nkeys; ++k) PDX_TRY(check_column(keys + k, "pdx_sort_indices", true));
+  if (n && !out->values) return fail(PDX_INVALID, "pdx_sort_indices: output too small");
+  out->length = n;
+  out->null_count = 0;
+  if (n == 0) return PDX_OK;
+  hipStream_t st = as_stream(stream);
+  Scratch s;
+  const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);
+  unsigned long long* pays[3];
+  for (auto& p : pays) p = s.get<unsigned long long>((size_t)n);
+  uint32_t* lo0 = s.get<uint32_t>((size_t)n);
+  uint32_t* lo1 = s.get<uint32_t>((size_t)n);
+  uint32_t* hist = s.get<uint32_t>((size_t)ntiles << 8);
+  uint32_t* chunk = s.get<uint32_t>((size_t)(nchunks + 1) << 8);
+  SortKeyStats* stats = s.get<SortKeyStats>((size_t)nkeys);
+  PDX_SCRATCH_CHECK(s);
+
+  SortKeyDescs all{};
+  all.n = nkeys;
+  for (int k = 0; k < nkeys; ++k) {
+    SortKeyDesc& d = all.k[k];
+    d.v = static_cast<const char*>(keys[k].values) + keys[k].offset * dtype_bytes(keys[k].dtype);
+    d.valid = validity_or_null(keys + k);
+    d.off = keys[k].offset;
+    d.dtype = keys[k].dtype;
+    d.descending = descending && descending[k];
+    d.cshift = -1;
+  }
+  SortKeyStats h[PDX_SORT_MAX_KEYS];
+  for (int k = 0; k < nkeys; ++k) h[k] = SortKeyStats{~0ull, 0ull, 0ull, 0ull};
+  PDX_HIP(hipMemcpyAsync(stats, h, sizeof(SortKeyStats) * (size_t)nkeys, hipMemcpyHostToDevice, st));
+  {
+    PDX_PROFILE("sort_key_stats", st);
+    hipLaunchKernelGGL(k_sort_key_stats, dim3(grid_for(n, 256, 4), nkeys), dim3(256), 0, st, all, n, stats);
+  }
+  PDX_LAUNCH_CHECK();
+  PDX_HIP(hipMemcpyAsync(h, stats, sizeof(SortKeyStats) * (size_t)nkeys, hipMemcpyDeviceToHost, st));
+  PDX_HIP(hipStreamSynchronize(st));
+
+  // the plan: fields from the least significant (the last key's value field) to the most significant (the first key's class field), packed
+  // greedily into rounds of at most 64 bits; a field is never split and a field of width 0 takes no part
+  struct Field {
+    int key, width;
+    bool is_class;
+  };
+  Field fields[2 * PDX_SORT_MAX_KEYS];
+  int nfields = 0, key_bits = 0;
+  for (int k = nkeys - 1; k >= 0; --k) {
+    if ((int64_t)(h[k].nans + h[k].nulls) > n || (h[k].min > h[k].max && (int64_t)(h[k].nans + h[k].nulls) != n))
+      return fail(PDX_DEVICE, "pdx_sort_indices: key statistics do not add up");
+    const unsigned long long range = h[k].min <= h[k].max ? h[k].max - h[k].min : 0ull;
+    const int w = range ? 64 - __builtin_clzll(range) : 0;
+    all.k[k].base = all.k[k].descending ? h[k].max : h[k].min;
+    if (w) fields[nfields++] = Field{k, w, false};
+    if (h[k].nans + h[k].nulls) fields[nfields++] = Field{k, 2, true};
+    key_bits += w + ((h[k].nans + h[k].nulls) ? 2 : 0);
+  }
+  const unsigned long long* sorted = nullptr;
+  int rounds = 0, passes = 0;
+  for (int f = 0; f < nfields || rounds == 0;) {  // (no field at all: one compose of key 0 numbers the rows)
+    SortKeyDescs rd{};
+    int bits = 0;
+    int slot_of_key[PDX_SORT_MAX_KEYS];
+    for (int& x : slot_of_key) x = -1;
+    for (; f < nfields && bits + fields[f].width <= 64; ++f) {
+      int& slot = slot_of_key[fields[f].key];
+      if (slot < 0) {
+        slot = rd.n++;
+        rd.k[slot] = all.k[fields[f].key];
+      }
+      if (fields[f].is_class) {
+        rd.k[slot].cshift = bits;
+      } else {
+        rd.k[slot].vshift = bits;
+        rd.k[slot].vwidth = fields[f].width;
+      }
+      bits += fields[f].width;
+    }
+    unsigned long long* in = pays[0] == sorted ? pays[1] : pays[0];
+    unsigned long long* tmp = pays[2] == in || pays[2] == sorted ? (pays[1] == in || pays[1] == sorted ? pays[0] : pays[1]) : pays[2];
+    {
+      PDX_PROFILE("sort_compose", st);
+      hipLaunchKernelGGL(k_sort_compose, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, rd, sorted, n, lo0, in);
+    }
+    PDX_LAUNCH_CHECK();
+    sorted = in;
+    if (bits == 0) break;
+    ++rounds;
+    if (n > 1) PDX_TRY(sort_packed64_in(lo0, in, lo1, tmp, hist, chunk, n, bits == 64 ? ~0ull : (1ull << bits) - 1ull, st, &sorted, &passes));
+  }
+  hipLaunchKernelGGL(k_pay_rows_u64, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, sorted, n, static_cast<unsigned long long*>(out->values));
+  PDX_LAUNCH_CHECK();
+  if (out->validity) PDX_HIP(hipMemsetAsync(out->validity, 0xFF, (size_t)((n + 7) / 8), st));
+  PDX_HIP(hipStreamSynchronize(st));
+  if (info) *info = pdx_sort_info{rounds, key_bits, passes, 0};
   return PDX_OK;
 }
 

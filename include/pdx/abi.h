@@ -127,7 +127,9 @@ typedef enum pdx_agg_kind {
    * validity buffer).  count_distinct: the number of distinct VALID values per group -> PDX_INT64, never null; float64 values
    * are distinct when their bit patterns are (0.0 / -0.0 and NaN payloads count separately, like Arrow's memo table).
    * GroupBy::min_max (src/dataframe.cpp:1602-1696) is {PDX_AGG_MIN, PDX_AGG_MAX} in one call. */
-  PDX_AGG_ALL = 10, PDX_AGG_ANY = 11, PDX_AGG_COUNT_DISTINCT = 12
+  PDX_AGG_ALL = 10, PDX_AGG_ANY = 11, PDX_AGG_COUNT_DISTINCT = 12,
+  /* pdx_row_aggregate only (every other entry point refuses it): count with CountOptions::ONLY_NULL, the null cells of a row */
+  PDX_AGG_COUNT_NULL = 13
 } pdx_agg_kind;
 typedef enum pdx_origin {
   PDX_ORIGIN_EPOCH = 0, PDX_ORIGIN_START_DAY = 1, PDX_ORIGIN_START = 2, PDX_ORIGIN_END = 3, PDX_ORIGIN_END_DAY = 4, PDX_ORIGIN_CUSTOM = 5,
@@ -276,6 +278,36 @@ int pdx_shift(const pdx_column* a, int64_t periods, const pdx_scalar* fill /* NU
  * fp64 sum reproduces Arrow's pairwise tree bit-for-bit (16-value leaves per valid run, binary-counter merge).
  * Synchronises `stream`. */
 int pdx_aggregate(int kind, const pdx_column* a, pdx_scalar* out, void* stream);
+
+/* ---------------------------------------------------------------- row-wise aggregates (axis = Columns)
+ * Replaces DataFrame::forAxis(name, AxisType::Columns, options) (src/dataframe.cpp:138-175: one GetScalar per cell, one ScalarArray::Make and
+ * one CallFunction per row) behind DataFrame::sum / mean / min / max / count / count_na / product / first / last / all / any / std / var
+ * (AxisType, ...) (src/dataframe.cpp:177-229).  For every row i, out[i] is what Arrow C++ 25.0.0's scalar aggregate `kind` returns for the
+ * ncols-element array [cols[0][i], ..., cols[ncols - 1][i]] under ScalarAggregateOptions{skip_nulls, min_count} (variance / stddev:
+ * VarianceOptions{ddof, skip_nulls, min_count}; count kinds take no option), bit for bit (tests/golden/rowagg_golden.npz) -- except the
+ * payload of a NaN that min / max / product / variance / stddev return.
+ *   kind : pdx_agg_kind SUM .. ANY and PDX_AGG_COUNT_NULL; PDX_AGG_COUNT_DISTINCT returns PDX_NOT_IMPLEMENTED.
+ *   cols : 1 <= ncols <= 2046 columns of ONE dtype and one length (PDX_INVALID otherwise: the reference's ScalarArray::Make fails on a row
+ *          of mixed types).  int64, uint64, float64, int32, float32: every kind but ALL / ANY (variance / stddev: int64 and float64, as
+ *          pdx_groupby_agg); bool: ALL, ANY, COUNT, COUNT_NULL; timestamp[ns]: MIN, MAX, FIRST, LAST, COUNT, COUNT_NULL.  Any other pair
+ *          returns PDX_NOT_IMPLEMENTED "Function 'sum' has no kernel matching input types (timestamp[ns])".  Any offset, validity at any
+ *          bit offset, null_count -1; a column without validity is all valid; length is int64.
+ *   out  : SUM, PRODUCT -> int64 for int64 / int32 (wrapping), uint64 for uint64, float64 for floats; MEAN, VARIANCE, STDDEV -> float64;
+ *          MIN, MAX, FIRST, LAST -> the input dtype; COUNT, COUNT_NULL -> int64, never null; ALL, ANY -> bool.  out->length >= the
+ *          columns' length, out->dtype as listed (PDX_INVALID otherwise).  out->validity may be NULL only when no row can be null for these
+ *          options and columns (PDX_INVALID otherwise).  Rows, bytes and validity bits of `out` beyond the columns' length are untouched;
+ *          value bytes under a null row are zero.
+ *   rules: a row is null when skip_nulls == 0 and it holds a null cell, or when fewer than min_count cells are valid; MIN / MAX / FIRST /
+ *          LAST also without a valid cell, VARIANCE / STDDEV with no more than ddof.  With min_count 0 a row without valid cells sums to 0,
+ *          multiplies to 1 and averages to NaN.  fp64 SUM / MEAN: Arrow's pairwise tree over the row in column order (float32 widened per
+ *          value, MEAN of integers over the values as doubles).  MIN / MAX skip NaN cells unless all are NaN; of 0.0 / -0.0 MIN keeps the
+ *          first, MAX the first in a row without null cells and the last in a row with one.  FIRST / LAST with skip_nulls == 0 are the first
+ *          / last CELL (null when that cell is null).  ALL / ANY with skip_nulls == 0: a valid false (true) decides the row, else a null
+ *          cell makes it null.
+ * One kernel launch reads every input byte once (twice for VARIANCE / STDDEV).  Nothing can fail at run time: the call is asynchronous on
+ * `stream`, except that out->null_count (always exact) is read back, as pdx_cumulative does, when a column carries a validity bitmap with
+ * null_count != 0 and the kind and options admit a null row. */
+int pdx_row_aggregate(int kind, const pdx_column* cols, int ncols, int skip_nulls, int64_t min_count, int ddof, pdx_mut_column* out, void* stream);
 
 /* ---------------------------------------------------------------- exact quantiles
  * Replaces CallFunction("quantile", {array}, QuantileOptions{q, interpolation, skip_nulls, min_count}): NDFrame::quantile

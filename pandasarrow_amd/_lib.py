@@ -28,6 +28,7 @@ SCALAR_NONE, SCALAR_RHS, SCALAR_LHS = range(3)  # pdx_scalar_side: which operand
 AGG_SUM, AGG_MEAN, AGG_MIN, AGG_MAX, AGG_COUNT = range(5)
 AGG_VARIANCE, AGG_STDDEV, AGG_PRODUCT, AGG_FIRST, AGG_LAST = range(5, 10)  # group-by only (include/pdx/abi.h)
 AGG_ALL, AGG_ANY, AGG_COUNT_DISTINCT = range(10, 13)  # group-by only: all / any need BOOL values
+AGG_COUNT_NULL = 13  # pdx_row_aggregate only: the null cells of a row (CountOptions::ONLY_NULL)
 ORIGIN_EPOCH, ORIGIN_START_DAY, ORIGIN_START, ORIGIN_END, ORIGIN_END_DAY, ORIGIN_CUSTOM = range(6)
 (UNIT_NANOSECOND, UNIT_MICROSECOND, UNIT_MILLISECOND, UNIT_SECOND, UNIT_MINUTE, UNIT_HOUR, UNIT_DAY, UNIT_WEEK, UNIT_MONTH,
  UNIT_QUARTER, UNIT_YEAR) = range(11)  # pdx_calendar_unit (YEAR: pdx_temporal_between only)
@@ -108,6 +109,7 @@ ABI_SYMBOLS = {
     "pdx_fill_null": (C.c_int, [C.c_int, _COL, _MUT, _P]),
     "pdx_shift": (C.c_int, [_COL, C.c_int64, C.POINTER(PdxScalar), _MUT, _P]),
     "pdx_aggregate": (C.c_int, [C.c_int, _COL, C.POINTER(PdxScalar), _P]),
+    "pdx_row_aggregate": (C.c_int, [C.c_int, _COL, C.c_int, C.c_int, C.c_int64, C.c_int, _MUT, _P]),
     "pdx_quantile": (C.c_int, [_COL, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(PdxScalar), _P]),
     "pdx_filter_count": (C.c_int, [_COL, C.c_int, C.POINTER(C.c_int64), _P]),
     "pdx_filter": (C.c_int, [_COL, C.c_int, _COL, C.c_int, _MUT, _P]),

@@ -656,7 +656,32 @@ class DataFrame:
         if len({c.dtype for c in self.cols}) > 1:  # arrow::ChunkedArray needs one type for all its chunks
             raise L.PdxError(L.INVALID, "frame-level aggregates need all columns to have the same dtype")
 
-    def sum(self):
+    # ---- aggregates along an axis (DataFrame::sum / mean / ... (AxisType, ...), src/dataframe.cpp:136-229): axis = "columns" (or 1) gives one
+    # value per row, a Series over the frame's index named "" -- one launch of pdx_row_aggregate with the reference's options (min_count = 0,
+    # so a row without valid cells sums to 0, multiplies to 1 and averages to NaN).  axis = "index" needs a string index of column names and
+    # whole-column product / first / last / variance kinds: not implemented.
+    def _along(self, what, axis, kind, skip_null=True, ddof=0):
+        if axis in ("index", 0):
+            raise L.PdxError(L.NOT_IMPLEMENTED, f"NotImplemented: DataFrame.{what}(axis='index') (one value per column) is not implemented")
+        if axis not in ("columns", 1):
+            raise L.PdxError(L.INVALID, f"DataFrame.{what}: axis must be 'index' or 'columns'")
+        return Series(K.row_aggregate(kind, self.cols, skip_null, 0, ddof), index=self.index, name="")
+
+    def product(self, axis, skip_null=True): return self._along("product", axis, L.AGG_PRODUCT, skip_null)
+    def first(self, axis, skip_null=True): return self._along("first", axis, L.AGG_FIRST, skip_null)
+    def last(self, axis, skip_null=True): return self._along("last", axis, L.AGG_LAST, skip_null)
+    def all(self, axis, skip_null=True): return self._along("all", axis, L.AGG_ALL, skip_null)
+    def any(self, axis, skip_null=True): return self._along("any", axis, L.AGG_ANY, skip_null)
+    def count_na(self, axis): return self._along("count_na", axis, L.AGG_COUNT_NULL)
+    def std(self, axis, ddof=1, skip_na=True): return self._along("std", axis, L.AGG_STDDEV, skip_na, ddof)
+    def var(self, axis, ddof=1, skip_na=True):
+        """the reference's var(axis) calls "stddev" as its std(axis) does (src/dataframe.cpp:215-229): mirrored; K.row_aggregate(L.AGG_VARIANCE, ...)
+        is the variance"""
+        return self._along("var", axis, L.AGG_STDDEV, skip_na, ddof)
+
+    def sum(self, axis=None, skip_null=True):
+        if axis is not None:
+            return self._along("sum", axis, L.AGG_SUM, skip_null)
         self._check_one_dtype()
         tot, first = None, True
         for c in self.cols:
@@ -672,11 +697,15 @@ class DataFrame:
             first = False
         return Scalar(tot)
 
-    def count(self):
+    def count(self, axis=None):
+        if axis is not None:
+            return self._along("count", axis, L.AGG_COUNT)
         return Scalar(sum(K.aggregate(L.AGG_COUNT, c)[0] for c in self.cols))
 
-    def mean(self):
+    def mean(self, axis=None, skip_null=True):
         """total of the per-chunk pairwise sums (int64 chunks are summed as doubles, like Arrow's mean) / total valid count"""
+        if axis is not None:
+            return self._along("mean", axis, L.AGG_MEAN, skip_null)
         self._check_one_dtype()
         tot, cnt = 0.0, 0
         for c in self.cols:
@@ -704,8 +733,8 @@ class DataFrame:
                 best = x
         return Scalar(best)
 
-    def min(self): return self._extreme(L.AGG_MIN)
-    def max(self): return self._extreme(L.AGG_MAX)
+    def min(self, axis=None, skip_null=True): return self._extreme(L.AGG_MIN) if axis is None else self._along("min", axis, L.AGG_MIN, skip_null)
+    def max(self, axis=None, skip_null=True): return self._extreme(L.AGG_MAX) if axis is None else self._along("max", axis, L.AGG_MAX, skip_null)
 
     # ---- where / take (src/dataframe.cpp:461-492)
     def where(self, mask: Series):

@@ -326,6 +326,29 @@ def aggregate(kind, a: Column):
     return int(s.v.i64), int(s.count)
 
 
+def row_result_dtype(kind, dtype):
+    """the dtype pdx_row_aggregate writes for `kind` over columns of `dtype` (include/pdx/abi.h)"""
+    if kind in (L.AGG_COUNT, L.AGG_COUNT_NULL):
+        return L.INT64
+    if kind in (L.AGG_ALL, L.AGG_ANY):
+        return L.BOOL
+    if kind in (L.AGG_MIN, L.AGG_MAX, L.AGG_FIRST, L.AGG_LAST):
+        return dtype
+    if kind in (L.AGG_SUM, L.AGG_PRODUCT):
+        return L.FLOAT64 if dtype in (L.FLOAT64, L.FLOAT32) else (L.UINT64 if dtype == L.UINT64 else L.INT64)
+    return L.FLOAT64
+
+
+def row_aggregate(kind, cols, skip_nulls=True, min_count=0, ddof=0) -> Column:
+    """Arrow's scalar aggregate `kind` over the cells of every row of `cols` (one dtype, one length): one kernel launch (pdx_row_aggregate)."""
+    if not cols:
+        raise L.PdxError(L.INVALID, "row_aggregate: at least one column is required")
+    out = Column.empty(row_result_dtype(kind, cols[0].dtype), cols[0].length, with_validity=kind not in (L.AGG_COUNT, L.AGG_COUNT_NULL))
+    m = out.mut()
+    L.check(L.load().pdx_row_aggregate(int(kind), _col_array(cols), len(cols), int(bool(skip_nulls)), int(min_count), int(ddof), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
 INTERPOLATIONS = {"linear": L.INTERP_LINEAR, "lower": L.INTERP_LOWER, "higher": L.INTERP_HIGHER, "nearest": L.INTERP_NEAREST,
                   "midpoint": L.INTERP_MIDPOINT}
 

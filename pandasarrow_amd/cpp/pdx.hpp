@@ -194,6 +194,9 @@ struct Scalar {
 enum class Interpolation { LINEAR = PDX_INTERP_LINEAR, LOWER = PDX_INTERP_LOWER, HIGHER = PDX_INTERP_HIGHER, NEAREST = PDX_INTERP_NEAREST,
                            MIDPOINT = PDX_INTERP_MIDPOINT };
 
+// pd::AxisType (src/core.h): Index = one value per column, Columns = one value per row
+enum class AxisType { Index, Columns };
+
 class DataFrame;
 struct GroupBy;
 struct Resampler;
@@ -966,6 +969,47 @@ class DataFrame {
   }
   Scalar min() const { return extreme(PDX_AGG_MIN); }
   Scalar max() const { return extreme(PDX_AGG_MAX); }
+
+  // DataFrame::forAxis(name, AxisType::Columns, options) (src/dataframe.cpp:138-175) and the calls built on it (177-229): Arrow's scalar
+  // aggregate over the cells of every row -- there one GetScalar per cell and one CallFunction per row, here one launch of pdx_row_aggregate.
+  // The result is a Series over the frame's index named "".  Mirrored from the reference: its Aggregation macro passes min_count = 0 (a row
+  // without valid cells sums to 0, multiplies to 1, averages to a valid NaN and has no min / max / first / last); count takes CountOptions'
+  // defaults; var(axis) calls "stddev" exactly as std(axis) does (src/dataframe.cpp:215-229), so it returns the standard deviation (the
+  // variance is pdx_row_aggregate(PDX_AGG_VARIANCE)).  A frame of mixed dtypes throws, as ScalarArray::Make does there.
+  // AxisType::Index would need a string index of column names and whole-column product / first / last / variance kinds: not implemented,
+  // like median / tdigest / nunique / quantile(axis) (the reference's quantile(axis) hands QuantileOptions to "stddev" and cannot succeed).
+  Series along(const char* what, AxisType axis, int kind, bool skip_null = true, int ddof = 0) const {
+    if (axis != AxisType::Columns)
+      throw std::runtime_error(std::string("NotImplemented: DataFrame::") + what + "(AxisType::Index) (one value per column) is not implemented");
+    if (m_columns.empty()) throw std::runtime_error(std::string("DataFrame::") + what + ": the frame has no columns");
+    std::vector<pdx_column> cols;
+    for (auto& c : m_columns) cols.push_back(c.c());
+    const int dt = m_columns[0].dtype;
+    const bool is_f = dt == PDX_FLOAT64 || dt == PDX_FLOAT32;
+    int out_dt = PDX_FLOAT64;
+    if (kind == PDX_AGG_COUNT || kind == PDX_AGG_COUNT_NULL) out_dt = PDX_INT64;
+    else if (kind == PDX_AGG_ALL || kind == PDX_AGG_ANY) out_dt = PDX_BOOL;
+    else if (kind == PDX_AGG_MIN || kind == PDX_AGG_MAX || kind == PDX_AGG_FIRST || kind == PDX_AGG_LAST) out_dt = dt;
+    else if (kind == PDX_AGG_SUM || kind == PDX_AGG_PRODUCT) out_dt = is_f ? PDX_FLOAT64 : dt == PDX_UINT64 ? PDX_UINT64 : PDX_INT64;
+    Array out = Array::Empty(out_dt, num_rows(), out_dt != PDX_INT64 || (kind != PDX_AGG_COUNT && kind != PDX_AGG_COUNT_NULL));
+    auto m = out.mut();
+    ThrowOnFailure(pdx_row_aggregate(kind, cols.data(), (int)cols.size(), skip_null ? 1 : 0, 0, ddof, &m, nullptr));
+    out.null_count = m.null_count;
+    return Series(out, m_index, "");
+  }
+  Series sum(AxisType axis, bool skip_null = true) const { return along("sum", axis, PDX_AGG_SUM, skip_null); }
+  Series mean(AxisType axis, bool skip_null = true) const { return along("mean", axis, PDX_AGG_MEAN, skip_null); }
+  Series min(AxisType axis, bool skip_null = true) const { return along("min", axis, PDX_AGG_MIN, skip_null); }
+  Series max(AxisType axis, bool skip_null = true) const { return along("max", axis, PDX_AGG_MAX, skip_null); }
+  Series product(AxisType axis, bool skip_null = true) const { return along("product", axis, PDX_AGG_PRODUCT, skip_null); }
+  Series first(AxisType axis, bool skip_null = true) const { return along("first", axis, PDX_AGG_FIRST, skip_null); }
+  Series last(AxisType axis, bool skip_null = true) const { return along("last", axis, PDX_AGG_LAST, skip_null); }
+  Series all(AxisType axis, bool skip_null = true) const { return along("all", axis, PDX_AGG_ALL, skip_null); }
+  Series any(AxisType axis, bool skip_null = true) const { return along("any", axis, PDX_AGG_ANY, skip_null); }
+  Series count(AxisType axis) const { return along("count", axis, PDX_AGG_COUNT); }
+  Series count_na(AxisType axis) const { return along("count_na", axis, PDX_AGG_COUNT_NULL); }
+  Series std(AxisType axis, int ddof = 1, bool skip_na = true) const { return along("std", axis, PDX_AGG_STDDEV, skip_na, ddof); }
+  Series var(AxisType axis, int ddof = 1, bool skip_na = true) const { return along("var", axis, PDX_AGG_STDDEV, skip_na, ddof); }
 
   DataFrame where(const Series& mask) const {
     if (mask.dtype() != PDX_BOOL) throw std::runtime_error("filter mask must be boolean");

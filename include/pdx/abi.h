@@ -57,8 +57,8 @@ typedef enum pdx_dtype {
   PDX_UINT64 = 3,
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
-   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile and pdx_sort_indices; every
-   * other entry point returns
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_sort_indices, pdx_row_aggregate
+   * and the selection / multiplexing calls (pdx_coalesce ... pdx_all_valid_mask); every other entry point returns
    * PDX_NOT_IMPLEMENTED naming the dtype.  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
    * widened (exactly) in v.f64. */
   PDX_INT32 = 5,
@@ -360,6 +360,59 @@ int pdx_take(const pdx_column* cols, int ncols, const pdx_column* indices, pdx_m
 /* Inverse of take: outs[c][indices[j]] = cols[c][j] (indices must be distinct and in [0, outs[c].length)); rows of outs
  * that no index names are left untouched.  Used to place per-owner group results by global group id. */
 int pdx_scatter(const pdx_column* cols, int ncols, const pdx_column* indices, pdx_mut_column* outs, void* stream);
+
+/* ---------------------------------------------------------------- selection / multiplexing and null handling
+ * Replaces the Arrow kernels behind DataFrame::coalesce (src/dataframe.cpp:1210-1225: "coalesce"), Series::clip (src/series.cpp:874-880:
+ * MaxElementWise over MinElementWise), Series::replace_with_mask (src/series.cpp:752-761), Series::indices_nonzero (src/series.cpp:365) and
+ * Series / DataFrame::drop_na (src/series.cpp:363, src/dataframe.cpp:1244-1252: "drop_null").  Semantics = Arrow C++ 25.0.0, bit for bit
+ * (tests/golden/multiplex_golden.npz).  Common to all: any offset, validity at any bit offset, null_count -1, a column without validity
+ * is all valid, int64 lengths; an empty input gives PDX_OK and length 0; out->length >= the result length and out->dtype as stated
+ * (PDX_INVALID otherwise); rows, bytes and validity bits of `out` beyond the result length are untouched; value bytes under a null row are
+ * zero; out->null_count is exact; deterministic.  The calls are asynchronous on `stream` except where a count is read back (named below).
+ *
+ * pdx_coalesce: out[i] = the first non-null of cols[0][i] .. cols[ncols - 1][i], null when every cell of the row is.  1 <= ncols <= 2046
+ *   columns of ONE dtype (any of the seven; the cells are copied as bits, so NaN payloads and -0.0 survive) and one length.  Mixed dtypes
+ *   return PDX_NOT_IMPLEMENTED naming the pair (Arrow would promote: cast first); unequal lengths PDX_INVALID.  out->validity may be NULL only
+ *   when cols[0] is all valid.  One launch: a wave reads the validity words of its rows first and loads values only from the columns that
+ *   give a row of them its value, so a frame whose first column is mostly valid moves about one column.  The null count is read back when
+ *   every column up to the last one that can matter carries a bitmap.
+ *
+ * pdx_element_wise_minmax: min_element_wise (is_max == 0) / max_element_wise of the operands under ElementWiseAggregateOptions{skip_nulls}.
+ *   Operands: 1 .. 2046 columns of ONE dtype -- int64, uint64, float64, int32, float32, timestamp[ns]; bool returns PDX_NOT_IMPLEMENTED
+ *   "Function 'min_element_wise' has no kernel matching input types (bool, bool)"; two dtypes PDX_NOT_IMPLEMENTED (the caller promotes) --
+ *   of length n = the longest, or of length 1 while n > 1: those are Arrow's scalars, broadcast.  Rules: with skip_nulls a row is null when
+ *   every operand is, without it when any is.  A NaN loses to any number and beats a null that is skipped; the result is NaN when every
+ *   valid cell is NaN; the payload of a returned NaN is not specified.  Arrow folds the scalars first and then the arrays, each in their
+ *   order, through fmin / fmax (accumulator, cell): of 0.0 / -0.0 the earlier of that order stays -- except that a float32 ARRAY cell
+ *   replaces an equal accumulator (the later stays) -- and a signalling NaN makes the accumulator NaN until a later number replaces it (a
+ *   signalling first scalar: for good).  out->validity may be NULL only when no row can be null (skip_nulls: an operand without validity;
+ *   otherwise no operand with validity).  The null count is read back when a row can be null.
+ * pdx_clip: max_element_wise(min_element_wise(x, hi), lo) -- the reference's nesting, each level applying skip_nulls on its own -- in one
+ *   read of x.  lo and hi are columns of length 1 (the reference's scalars), which may be null: with skip_nulls a null bound does not
+ *   bound, without it every row is null.  lo > hi gives lo; a NaN bound does not bound.  Same dtypes, same kernel template.
+ *
+ * pdx_replace_with_mask: out[i] = repl[k] where mask[i] is valid and true, k = the number of valid true mask rows before i (null where
+ *   repl[k] is null); null where mask[i] is null; a[i] otherwise.  All seven dtypes.  PDX_INVALID: mask->length != a->length "Mask must be
+ *   of same length as array (expected N items but got M items)"; repl->length below the number of valid true mask rows "Replacement array
+ *   must be of appropriate length (expected N items but got M items)" (a longer repl is accepted, its tail ignored; `out` is unspecified
+ *   after this failure); repl->dtype != a->dtype, as Arrow has no kernel for a mixed pair.  The count of valid true mask rows is read back
+ *   once, together with the null count: the call's only host wait.
+ *
+ * pdx_indices_nonzero_count / pdx_indices_nonzero: the ascending row indices, PDX_UINT64 and never null, of the rows that are valid and not
+ *   zero (bool: true; floats: NaN counts, -0.0 does not).  int64, uint64, float64, int32, float32, bool; timestamp[ns] returns
+ *   PDX_NOT_IMPLEMENTED "Function 'indices_nonzero' has no kernel matching input types (timestamp[ns])".  Two calls as pdx_filter_count /
+ *   pdx_filter: the count (host-visible), then the fill into out->length >= count rows; both wait for the count.
+ *
+ * pdx_all_valid_mask: out_mask is a PDX_BOOL column without nulls (its validity is not touched, null_count = 0) whose bit i is set when
+ *   every column is valid at row i: the rows drop_null keeps.  1 .. 2046 columns of any dtypes and one length.  drop_na = this mask, then
+ *   pdx_filter with emit_null = 0. */
+int pdx_coalesce(const pdx_column* cols, int ncols, pdx_mut_column* out, void* stream);
+int pdx_element_wise_minmax(int is_max, const pdx_column* cols, int ncols, int skip_nulls, pdx_mut_column* out, void* stream);
+int pdx_clip(const pdx_column* x, const pdx_column* lo, const pdx_column* hi, int skip_nulls, pdx_mut_column* out, void* stream);
+int pdx_replace_with_mask(const pdx_column* a, const pdx_column* mask, const pdx_column* repl, pdx_mut_column* out, void* stream);
+int pdx_indices_nonzero_count(const pdx_column* a, int64_t* out_count, void* stream);
+int pdx_indices_nonzero(const pdx_column* a, pdx_mut_column* out, void* stream);
+int pdx_all_valid_mask(const pdx_column* cols, int ncols, pdx_mut_column* out_mask, void* stream);
 
 /* ---------------------------------------------------------------- group-by
  * pdx_groupby_create replaces GroupBy::makeGroups (src/dataframe.cpp:1571-1600): Grouper::Make + Consume

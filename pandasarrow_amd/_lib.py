@@ -110,6 +110,13 @@ ABI_SYMBOLS = {
     "pdx_shift": (C.c_int, [_COL, C.c_int64, C.POINTER(PdxScalar), _MUT, _P]),
     "pdx_aggregate": (C.c_int, [C.c_int, _COL, C.POINTER(PdxScalar), _P]),
     "pdx_row_aggregate": (C.c_int, [C.c_int, _COL, C.c_int, C.c_int, C.c_int64, C.c_int, _MUT, _P]),
+    "pdx_coalesce": (C.c_int, [_COL, C.c_int, _MUT, _P]),
+    "pdx_element_wise_minmax": (C.c_int, [C.c_int, _COL, C.c_int, C.c_int, _MUT, _P]),
+    "pdx_clip": (C.c_int, [_COL, _COL, _COL, C.c_int, _MUT, _P]),
+    "pdx_replace_with_mask": (C.c_int, [_COL, _COL, _COL, _MUT, _P]),
+    "pdx_indices_nonzero_count": (C.c_int, [_COL, C.POINTER(C.c_int64), _P]),
+    "pdx_indices_nonzero": (C.c_int, [_COL, _MUT, _P]),
+    "pdx_all_valid_mask": (C.c_int, [_COL, C.c_int, _MUT, _P]),
     "pdx_quantile": (C.c_int, [_COL, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(PdxScalar), _P]),
     "pdx_filter_count": (C.c_int, [_COL, C.c_int, C.POINTER(C.c_int64), _P]),
     "pdx_filter": (C.c_int, [_COL, C.c_int, _COL, C.c_int, _MUT, _P]),

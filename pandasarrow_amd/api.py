@@ -385,6 +385,43 @@ class Series:
             return self.where(s) if s.col.dtype == L.BOOL else self.take(s)
         raise TypeError("only Series selectors are on the hot path")
 
+    # ---- selection / multiplexing and null handling (src/series.cpp:363-365, 752-761, 874-880)
+    def _wrap_shorter(self, col):
+        """ReturnSeriesOrThrowOnError (src/series.cpp:1364-1384) for a result that may be shorter than the index: an empty result or an
+        implicit index gives no index; a shorter result keeps the LAST `length` labels (idx->Slice(indexLength - arrayLength))"""
+        if self.index is None or col.length == 0 or self.index.length == 0:
+            return Series(col, name="")
+        if col.length > self.index.length:
+            raise L.PdxError(L.INVALID, f"ReturnSeriesOrThrowOnError requires new Array length({col.length}) <= original index Length({self.index.length})")
+        return Series(col, index=self.index.slice(self.index.length - col.length, col.length), name="")
+
+    def _bound(self, x, dtype):
+        """a clip bound as a column of length 1: a Scalar / number, None for the null scalar"""
+        if isinstance(x, Scalar):
+            x = x.value
+        if isinstance(x, Column):
+            return x if x.dtype == dtype else K.cast(x, dtype)
+        host = {L.FLOAT64: np.float64, L.FLOAT32: np.float32, L.UINT64: np.uint64, L.INT32: np.int32}.get(dtype, np.int64)
+        return Column.from_numpy(np.array([0 if x is None else x], host), None if x is not None else np.zeros(1, bool), dtype=dtype)
+
+    def clip(self, x: "Series", min, max, skip_null=True):
+        """Series::clip(x, min, max, skipNull): max_element_wise(min_element_wise(x, max), min) over x's index, in one read of x (pdx_clip)"""
+        return Series(K.clip(x.col, self._bound(min, x.col.dtype), self._bound(max, x.col.dtype), skip_null), index=x.index, name="")
+
+    def replace_with_mask(self, cond: "Series", other: "Series"):
+        if not (cond.size() == other.size() and other.size() <= self.size()):
+            raise L.PdxError(L.INVALID, "replace_with_mask error: valid precondition (cond.size() == other.size()) and (other.size() <= this->size())")
+        return self._wrap(K.replace_with_mask(self.col, cond.col, other.col))
+
+    def drop_na(self):
+        """Series::drop_na ("drop_null" on the array): pdx_all_valid_mask, then pdx_filter"""
+        if self.col.dtype == L.BOOL:
+            raise L.PdxError(L.NOT_IMPLEMENTED, "NotImplemented: drop_na of a boolean Series (pdx_filter takes no boolean columns)")
+        return self._wrap_shorter(K.drop_na([self.col])[0])
+
+    def indices_nonzero(self):
+        return self._wrap_shorter(K.indices_nonzero(self.col))
+
     # ---- sort (src/series.cpp:864-868, 978-992, 1211-1229)
     def argsort(self, ascending=True):
         """Series::argsort: CallFunction("array_sort_indices") -> uint64 indices (re-attached index per ReturnSeriesOrThrowOnError)."""
@@ -735,6 +772,31 @@ class DataFrame:
 
     def min(self, axis=None, skip_null=True): return self._extreme(L.AGG_MIN) if axis is None else self._along("min", axis, L.AGG_MIN, skip_null)
     def max(self, axis=None, skip_null=True): return self._extreme(L.AGG_MAX) if axis is None else self._along("max", axis, L.AGG_MAX, skip_null)
+
+    # ---- coalesce / drop_na (src/dataframe.cpp:1210-1225, 1244-1252)
+    def coalesce(self, columns=None):
+        """per row the first non-null cell, of all columns or of `columns` in the order given: one launch of pdx_coalesce.  Columns of
+        different numeric dtypes are first cast to Arrow's common type where pdx_cast has that cast."""
+        cols = self.cols if columns is None else [self.cols[self.names.index(nm)] for nm in columns]
+        if not cols:
+            raise L.PdxError(L.INVALID, "coalesce: at least one column is required")
+        if len({c.dtype for c in cols}) > 1:
+            if any(c.dtype in (L.BOOL, L.TIMESTAMP_NS, L.UINT64) for c in cols):
+                raise L.PdxError(L.NOT_IMPLEMENTED, "NotImplemented: coalesce of columns of these different dtypes (no cast to a common type)")
+            dt = cols[0].dtype
+            for c in cols[1:]:
+                dt = K.promote_dtype(dt, c.dtype)
+            cols = [c if c.dtype == dt else K.cast(c, dt) for c in cols]
+        return Series(K.coalesce(cols), index=self.index, name="")
+
+    def drop_na(self):
+        """the rows without a null in any column (the index among them, as the reference appends it to the batch): pdx_all_valid_mask,
+        then pdx_filter over the columns and the index -- every column is read once"""
+        cols = self.cols + ([self.index] if self.index is not None else [])
+        if not cols:
+            return self
+        outs = K.drop_na(cols)
+        return self._like(outs[: len(self.cols)], index=outs[-1] if self.index is not None else None)
 
     # ---- where / take (src/dataframe.cpp:461-492)
     def where(self, mask: Series):

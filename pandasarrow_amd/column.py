@@ -445,6 +445,74 @@ def concat(parts) -> Column:
     return out._adopt(m)
 
 
+# ---------------------------------------------------------------- selection / multiplexing, null handling
+def coalesce(cols) -> Column:
+    """per row the first non-null cell of `cols` (one dtype, one length), null when all are: one kernel launch (pdx_coalesce)"""
+    if not cols:
+        raise L.PdxError(L.INVALID, "coalesce: at least one column is required")
+    out = Column.empty(cols[0].dtype, cols[0].length, with_validity=cols[0].has_nulls())
+    m = out.mut()
+    L.check(L.load().pdx_coalesce(_col_array(cols), len(cols), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def element_wise_minmax(is_max, cols, skip_nulls=True) -> Column:
+    """min_element_wise / max_element_wise of `cols` (one dtype; length n, or 1 = a broadcast scalar) (pdx_element_wise_minmax)"""
+    if not cols:
+        raise L.PdxError(L.INVALID, "element_wise_minmax: at least one operand is required")
+    out = Column.empty(cols[0].dtype, max(c.length for c in cols), with_validity=any(c.has_nulls() for c in cols))
+    m = out.mut()
+    L.check(L.load().pdx_element_wise_minmax(int(bool(is_max)), _col_array(cols), len(cols), int(bool(skip_nulls)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def clip(x: Column, lo: Column, hi: Column, skip_nulls=True) -> Column:
+    """max_element_wise(min_element_wise(x, hi), lo) in one read of x; lo / hi: columns of length 1, which may be null (pdx_clip)"""
+    out = Column.empty(x.dtype, x.length, with_validity=x.has_nulls() or lo.has_nulls() or hi.has_nulls())
+    cx, cl, ch, m = x.c(), lo.c(), hi.c(), out.mut()
+    L.check(L.load().pdx_clip(C.byref(cx), C.byref(cl), C.byref(ch), int(bool(skip_nulls)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def replace_with_mask(a: Column, mask: Column, repl: Column) -> Column:
+    """the rows of `a` where `mask` is true replaced by the values of `repl` in their order (pdx_replace_with_mask)"""
+    out = Column.empty(a.dtype, a.length, with_validity=a.has_nulls() or mask.has_nulls() or repl.has_nulls())
+    ca, cm, cr, m = a.c(), mask.c(), repl.c(), out.mut()
+    L.check(L.load().pdx_replace_with_mask(C.byref(ca), C.byref(cm), C.byref(cr), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def indices_nonzero(a: Column) -> Column:
+    """uint64 ascending rows of `a` that are valid and not zero (pdx_indices_nonzero_count + pdx_indices_nonzero)"""
+    lib = L.load()
+    cnt = C.c_int64(0)
+    ca = a.c()
+    L.check(lib.pdx_indices_nonzero_count(C.byref(ca), C.byref(cnt), _stream()))
+    out = Column.empty(L.UINT64, int(cnt.value))
+    m = out.mut()
+    L.check(lib.pdx_indices_nonzero(C.byref(ca), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def all_valid_mask(cols) -> Column:
+    """BOOL column without nulls: row i is set when every column of `cols` is valid there (pdx_all_valid_mask)"""
+    if not cols:
+        raise L.PdxError(L.INVALID, "all_valid_mask: at least one column is required")
+    out = Column.empty(L.BOOL, cols[0].length)
+    m = out.mut()
+    L.check(L.load().pdx_all_valid_mask(_col_array(cols), len(cols), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def drop_na(cols):
+    """the rows at which every column of `cols` is valid: pdx_all_valid_mask, then one pdx_filter over all of them (16 columns a call)"""
+    mask = all_valid_mask(cols)
+    outs = []
+    for c0 in range(0, len(cols), 16):
+        outs += filter(cols[c0:c0 + 16], mask, emit_null=False)
+    return outs
+
+
 # ---------------------------------------------------------------- temporal rounding (DataFrame::downsample)
 def round_temporal(ts: Column, multiple, unit, ceil=False, week_starts_monday=True, calendar_based_origin=False, nearest=False) -> Column:
     """floor_temporal / ceil_temporal / round_temporal (nearest) of a timestamp[ns] column (pdx_round_temporal)."""

@@ -458,6 +458,41 @@ class Series {
   }
   Series operator[](const Series& s) const { return s.dtype() == PDX_BOOL ? where(s) : take(s); }
 
+  // ---- selection / multiplexing and null handling (src/series.cpp:363-365, 752-761, 874-880)
+  // Series::clip(x, min, max, skipNull): MaxElementWise({MinElementWise({x, max}), min}) over x's index -- one read of x (pdx_clip)
+  Series clip(const Series& x, const Scalar& min, const Scalar& max, bool skipNull = true) const {
+    Array lo = bound(min, x.dtype()), hi = bound(max, x.dtype());
+    Array out = Array::Empty(x.dtype(), x.size(), x.m_array.has_nulls() || lo.has_nulls() || hi.has_nulls());
+    auto cx = x.m_array.c(), cl = lo.c(), ch = hi.c();
+    auto m = out.mut();
+    ThrowOnFailure(pdx_clip(&cx, &cl, &ch, skipNull ? 1 : 0, &m, nullptr));
+    out.null_count = m.null_count;
+    return Series(out, x.m_index, "");
+  }
+  Series replace_with_mask(const Series& cond, const Series& other) const {
+    if (!(cond.size() == other.size() && other.size() <= size()))
+      throw std::runtime_error("replace_with_mask error: valid precondition (cond.size() == other.size()) and (other.size() <= this->size())");
+    Array out = Array::Empty(dtype(), size(), m_array.has_nulls() || cond.m_array.has_nulls() || other.m_array.has_nulls());
+    auto ca = m_array.c(), cm = cond.m_array.c(), cr = other.m_array.c();
+    auto m = out.mut();
+    ThrowOnFailure(pdx_replace_with_mask(&ca, &cm, &cr, &m, nullptr));
+    out.length = m.length;
+    out.null_count = m.null_count;
+    return wrap(out);
+  }
+  // "drop_null" on the array: pdx_all_valid_mask, then pdx_filter
+  Series drop_na() const { return wrap_shorter(run_drop_null({m_array})[0]); }
+  Series indices_nonzero() const {
+    auto ca = m_array.c();
+    int64_t count = 0;
+    ThrowOnFailure(pdx_indices_nonzero_count(&ca, &count, nullptr));
+    Array out = Array::Empty(PDX_UINT64, count, false);
+    auto m = out.mut();
+    ThrowOnFailure(pdx_indices_nonzero(&ca, &m, nullptr));
+    out.length = m.length;
+    return wrap_shorter(out);
+  }
+
   // ---- sort (src/series.cpp:864-868, 978-992, 1211-1229): CallFunction("array_sort_indices") + Take of values and index + Slice
   Series argsort(bool ascending = true) const {
     Array idx = Array::Empty(PDX_UINT64, size(), false);
@@ -599,6 +634,29 @@ class Series {
     for (size_t i = 0; i < outs.size(); ++i) outs[i].null_count = mo[i].null_count;
     return outs;
   }
+  // the rows at which every column is valid ("drop_null" of a batch): one mask over all columns, then pdx_filter 16 columns a call
+  static std::vector<Array> run_drop_null(const std::vector<Array>& cols) {
+    std::vector<pdx_column> in;
+    for (auto& c : cols) in.push_back(c.c());
+    Array mask = Array::Empty(PDX_BOOL, cols.empty() ? 0 : cols[0].length, false);
+    auto mm = mask.mut();
+    ThrowOnFailure(pdx_all_valid_mask(in.data(), (int)in.size(), &mm, nullptr));
+    auto cm = mask.c();
+    int64_t kept = 0;
+    ThrowOnFailure(pdx_filter_count(&cm, /*emit_null=*/0, &kept, nullptr));
+    std::vector<Array> outs;
+    for (size_t at = 0; at < cols.size(); at += 16) {
+      const size_t k = std::min<size_t>(16, cols.size() - at);
+      std::vector<pdx_mut_column> mo;
+      for (size_t i = 0; i < k; ++i) {
+        outs.push_back(Array::Empty(cols[at + i].dtype, kept, cols[at + i].has_nulls()));
+        mo.push_back(outs.back().mut());
+      }
+      ThrowOnFailure(pdx_filter(in.data() + at, (int)k, &cm, /*emit_null=*/0, mo.data(), nullptr));
+      for (size_t i = 0; i < k; ++i) outs[at + i].null_count = mo[i].null_count;
+    }
+    return outs;
+  }
   static std::vector<Array> run_take(const std::vector<Array>& cols, const Array& idx) {
     std::vector<pdx_column> in;
     for (auto& c : cols) in.push_back(c.c());
@@ -617,6 +675,30 @@ class Series {
  private:
   // ReturnSeriesOrThrowOnError (src/series.cpp:1364-1384): equal length -> same index; the result name is reset to ""
   Series wrap(Array a) const { return Series(std::move(a), m_index, ""); }
+  // ... an empty result or no index -> no index; a shorter result keeps the LAST `length` labels (idx->Slice(indexLength - arrayLength))
+  Series wrap_shorter(Array a) const {
+    if (!m_index || a.length == 0 || m_index->length == 0) return Series(std::move(a), std::nullopt, "");
+    if (a.length > m_index->length) throw std::runtime_error("ReturnSeriesOrThrowOnError requires new Array length <= original index Length");
+    Array idx = *m_index;
+    idx.offset += idx.length - a.length;
+    idx.length = a.length;
+    if (idx.validity) idx.null_count = -1;
+    return Series(std::move(a), idx, "");
+  }
+  // a clip bound as a column of length 1 of x's dtype (a null Scalar: the null scalar)
+  static Array bound(const Scalar& s, int dtype) {
+    Scalar v = s;
+    if (dtype == PDX_FLOAT64 && v.s.dtype != PDX_FLOAT64) {
+      v.s.v.f64 = (double)v.s.v.i64;
+      v.s.dtype = PDX_FLOAT64;
+    } else if (dtype != PDX_FLOAT64 && v.s.dtype == PDX_FLOAT64) {
+      if (v.s.is_valid) throw std::runtime_error("clip: a float64 bound for a column that is not float64");
+      v.s.dtype = PDX_INT64;
+    }
+    Array a = v.to_array();
+    a.dtype = dtype;  // (uint64 / timestamp bounds travel as their 64-bit patterns)
+    return a;
+  }
   std::vector<Array> columns_with_index() const {
     std::vector<Array> cols{m_array};
     if (m_index) cols.push_back(*m_index);
@@ -1011,6 +1093,22 @@ class DataFrame {
   Series std(AxisType axis, int ddof = 1, bool skip_na = true) const { return along("std", axis, PDX_AGG_STDDEV, skip_na, ddof); }
   Series var(AxisType axis, int ddof = 1, bool skip_na = true) const { return along("var", axis, PDX_AGG_STDDEV, skip_na, ddof); }
 
+  // DataFrame::coalesce() / coalesce(columns) (src/dataframe.cpp:1210-1225): per row the first non-null cell, one launch of pdx_coalesce.
+  // int64 columns among float64 ones are cast first (Arrow's implicit promotion, pdx_cast_f64 checked); other mixtures throw.
+  Series coalesce() const { return coalesce_of(m_columns); }
+  Series coalesce(const std::vector<std::string>& columns) const {
+    std::vector<Array> cols;
+    for (auto& nm : columns) cols.push_back(m_columns[(size_t)column_index(nm)]);
+    return coalesce_of(cols);
+  }
+  // DataFrame::drop_na (src/dataframe.cpp:1244-1252): DropNull of the batch with the index appended -- the rows without a null in any
+  // column or in the index; the index rows follow the kept rows
+  DataFrame drop_na() const {
+    if (m_columns.empty()) return *this;
+    auto outs = Series::run_drop_null(columns_with_index());
+    return rebuild(outs);
+  }
+
   DataFrame where(const Series& mask) const {
     if (mask.dtype() != PDX_BOOL) throw std::runtime_error("filter mask must be boolean");
     auto outs = Series::run_filter(columns_with_index(), mask.m_array);
@@ -1210,6 +1308,31 @@ class DataFrame {
     std::vector<Array> cols = m_columns;
     if (m_index) cols.push_back(*m_index);
     return cols;
+  }
+  Series coalesce_of(std::vector<Array> cols) const {
+    if (cols.empty()) throw std::runtime_error("coalesce: at least one column is required");
+    bool any_f = false, any_i = false;
+    for (auto& c : cols) {
+      any_f = any_f || c.dtype == PDX_FLOAT64;
+      any_i = any_i || c.dtype == PDX_INT64;
+    }
+    if (any_f && any_i)
+      for (auto& c : cols)
+        if (c.dtype == PDX_INT64) {
+          Array f = Array::Empty(PDX_FLOAT64, c.length, c.has_nulls());
+          auto ci = c.c();
+          auto mf = f.mut();
+          ThrowOnFailure(pdx_cast_f64(&ci, /*checked=*/1, &mf, nullptr));
+          f.null_count = mf.null_count;
+          c = f;
+        }
+    std::vector<pdx_column> in;
+    for (auto& c : cols) in.push_back(c.c());
+    Array out = Array::Empty(cols[0].dtype, cols[0].length, cols[0].has_nulls());
+    auto m = out.mut();
+    ThrowOnFailure(pdx_coalesce(in.data(), (int)in.size(), &m, nullptr));
+    out.null_count = m.null_count;
+    return Series(out, m_index, "");
   }
   DataFrame rebuild(std::vector<Array>& outs) const {
     std::optional<Array> idx;

@@ -57,9 +57,9 @@ typedef enum pdx_dtype {
   PDX_UINT64 = 3,
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
-   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_sort_indices, pdx_row_aggregate
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_mode, pdx_sort_indices, pdx_row_aggregate
    * and the selection / multiplexing calls (pdx_coalesce ... pdx_all_valid_mask); every other entry point returns
-   * PDX_NOT_IMPLEMENTED naming the dtype.  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
+   * PDX_NOT_IMPLEMENTED naming the dtype (the group-by does not take 4-byte keys yet, so value_counts of such a column is refused too).  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
    * widened (exactly) in v.f64. */
   PDX_INT32 = 5,
   PDX_FLOAT32 = 6
@@ -483,6 +483,45 @@ int pdx_groupby_last_plan(const pdx_groupby* gb, char* buf, size_t buf_len);
 /* GroupBy::quantile (src/group_by.h:123-124, src/dataframe.cpp:1867-1931): see "exact quantiles" above. */
 int pdx_groupby_quantile(pdx_groupby* gb, const pdx_column* values, const double* q, int nq, int interpolation,
                          int skip_nulls, int64_t min_count, pdx_mut_column* outs /* nq columns of >= G rows */, void* stream);
+
+/* ---------------------------------------------------------------- value frequencies
+ * pdx_mode replaces CallFunction("mode", {array}, ModeOptions{n, skip_nulls, min_count}) reached from NDFrame::mode (src/ndframe.h:63-66, 255,
+ * src/ndframe.cpp:177-197); pdx_groupby_mode is what GroupBy::mode (src/group_by.h:126-127, src/dataframe.cpp:1808-1865) intends: Arrow's mode
+ * with default options over every group's rows; pdx_groupby_sizes is the counts half of Series::value_counts (src/dataframe.cpp:1093-1100),
+ * beside pdx_groupby_unique_keys.  Semantics = Arrow C++ 25.0.0 (tests/golden/mode_golden.npz):
+ *   - the result is the k = min(n, number of distinct values) most frequent valid values as (mode, count) pairs, ordered by count descending,
+ *     ties by value ascending.  Nulls take no part.
+ *   - floats: -0.0 == 0.0 is one value (their counts add); every NaN of any sign or payload is one value, sorts above +inf in the tie order,
+ *     takes part like any other value and is returned as the canonical quiet NaN (0x7ff8000000000000 / 0x7fc00000).  The zero returned from a
+ *     column that holds both zeros is the one that comes first in ROW order (pdx_quantile's convention; Arrow returns whichever zero its
+ *     unstable sort left first).
+ *   - the result is empty (k = 0) when there is no valid value, when skip_nulls == 0 and the column holds a null, or when fewer than
+ *     min_count rows are valid (NaN rows count as valid).
+ *   - n <= 0: PDX_INVALID "ModeOptions::n must be strictly positive", before anything is launched.
+ *   - a: PDX_INT64, PDX_UINT64, PDX_FLOAT64, PDX_INT32, PDX_FLOAT32, PDX_BOOL (false < true).  PDX_TIMESTAMP_NS returns PDX_NOT_IMPLEMENTED
+ *     "Function 'mode' has no kernel matching input types (timestamp[ns])".
+ * pdx_mode: any offset, validity at any bit offset, null_count -1; at most 2^31-1 rows (PDX_NOT_IMPLEMENTED beyond).  out_modes->dtype ==
+ * a->dtype, out_counts->dtype == PDX_INT64, both capacities >= min(n, a->length); anything else is PDX_INVALID before a launch.  On return
+ * both lengths are k, null_count 0 (validity may be NULL, it is not written); rows and bytes beyond k are untouched (bool modes: bits
+ * beyond k).  Synchronises `stream` like pdx_aggregate (k is host-visible); deterministic (same bits on any stream / run).
+ * Two paths behind one first read (valid rows, smallest / largest value): bool and integer columns whose max - min + 1 <= 8192 are counted
+ * (a second read into a workgroup-private LDS histogram); everything else is sorted (pdx_argsort / pdx_sort_indices), the runs of equal
+ * values are marked and compacted.  pdx_mode_last_plan (diagnostic, this thread's last pdx_mode; tests assert it so that a moved threshold
+ * fails a test): "path=count bins=<threshold> width=<max - min + 1>" | "path=sort runs=<distinct values>" | "path=bool" | "path=empty".
+ * pdx_groupby_mode: handles from pdx_groupby_create / pdx_resample_create / pdx_downsample_create; values PDX_INT64 / PDX_UINT64 /
+ * PDX_FLOAT64 (others: PDX_NOT_IMPLEMENTED naming the dtype); outputs of >= G rows, the values' dtype and PDX_INT64.  n = 1, skip_nulls,
+ * min_count 0 per group.  A group without a valid value gets a null mode (validity bit clear, value bytes zero) and count 0;
+ * out_modes->validity is required when such a group exists (PDX_INVALID otherwise: known only after the groups have been reduced,
+ * so the output buffers have been written and both outputs come back with length 0); null_count is exact.  Neither the bound-column cache
+ * nor pdx_groupby_last_plan is touched.
+ * pdx_groupby_sizes: the rows of every group in group-id order, the null key's group included (out_sizes: G int64, device).  Served from
+ * the sizes the handle holds (a COUNT of a column without nulls leaves them there); a handle that does not hold them yet takes them from
+ * its segment boundaries or computes them through that same COUNT (which reads no value column) and keeps them: later calls, and later
+ * COUNTs of columns without nulls, copy them. */
+int pdx_mode(const pdx_column* a, int64_t n, int skip_nulls, int64_t min_count, pdx_mut_column* out_modes, pdx_mut_column* out_counts, void* stream);
+int pdx_mode_last_plan(char* buf, size_t buf_len);
+int pdx_groupby_mode(pdx_groupby* gb, const pdx_column* values, pdx_mut_column* out_modes, pdx_mut_column* out_counts, void* stream);
+int pdx_groupby_sizes(pdx_groupby* gb, int64_t* out_sizes /* G int64, device */, void* stream);
 
 /* ---------------------------------------------------------------- exact multi-GPU fp64 sum (partial-tree exchange)
  * The reference's per-group sum is Arrow's pairwise tree over the group's rows in GLOBAL row order; with row-range shards a

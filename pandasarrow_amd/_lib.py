@@ -138,6 +138,10 @@ ABI_SYMBOLS = {
     "pdx_groupby_bound_bytes": (C.c_int64, [_P]),
     "pdx_groupby_last_plan": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
     "pdx_groupby_quantile": (C.c_int, [_P, _COL, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int64, _MUT, _P]),
+    "pdx_mode": (C.c_int, [_COL, C.c_int64, C.c_int, C.c_int64, _MUT, _MUT, _P]),
+    "pdx_mode_last_plan": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "pdx_groupby_mode": (C.c_int, [_P, _COL, _MUT, _MUT, _P]),
+    "pdx_groupby_sizes": (C.c_int, [_P, _P, _P]),
     "pdx_groupby_group_values": (C.c_int, [_P, _COL, _P, C.POINTER(_P)]),
     "pdx_grouped_destroy": (C.c_int, [_P]),
     "pdx_grouped_counts": (C.c_int, [_P, _P, _P]),

@@ -136,6 +136,19 @@ class Scalar:
     def __ne__(self, o): return self._cmp(L.NE, o) if isinstance(o, (Series, DataFrame)) else not self.__eq__(o)
 
 
+class Mode:
+    """One entry of Series.mode: the value (Scalar) and how many rows hold it."""
+
+    __slots__ = ("mode", "count")
+
+    def __init__(self, mode, count):
+        self.mode = mode
+        self.count = count
+
+    def __repr__(self):
+        return f"Mode({self.mode!r}, {self.count})"
+
+
 class Series:
     def __init__(self, values, valid=None, index=None, name="", is_index=False, dtype=None):
         """dtype: None infers it (float32 arrays stay float32, int32 arrays widen to int64); L.INT32 / L.FLOAT32 keep 4-byte values."""
@@ -308,6 +321,25 @@ class Series:
         many = isinstance(q, (list, tuple))
         res = [Scalar(v, c) for v, c in K.quantile(self.col, list(q) if many else [q], interpolation, skip_nulls, min_count)]
         return res if many else res[0]
+
+    def mode(self, n=1, skip_nulls=True, min_count=0):
+        """NDFrame::mode (src/ndframe.h:63-66, src/ndframe.cpp:177-197): Arrow's mode -- the min(n, distinct) most frequent valid values by
+        count descending, ties by value ascending.  -> list of Mode(mode: Scalar, count: int); empty when Arrow's result is empty."""
+        modes, counts = K.mode(self.col, n, skip_nulls, min_count)
+        if modes.length == 0:
+            return []
+        mv, cv = modes.to_numpy()[0], counts.to_numpy()[0]
+        return [Mode(Scalar(v.item(), int(c)), int(c)) for v, c in zip(mv, cv)]
+
+    def value_counts(self):
+        """Series::value_counts (src/dataframe.cpp:1093-1100): the distinct values in first-occurrence order (a null is one entry) and
+        their counts -> DataFrame with columns "values", "counts"."""
+        v, c = K.value_counts(self.col)
+        return DataFrame({"values": v, "counts": c})
+
+    def is_unique(self):
+        """Series::is_unique (src/series.cpp:1243): unique().size() == size()."""
+        return K.is_unique(self.col)
 
     def count_na(self):
         """NDFrame::count_na (src/ndframe.cpp:119-126): CountOptions::ONLY_NULL."""
@@ -1135,6 +1167,15 @@ class GroupBy:
             raise L.PdxError(L.INVALID, "GroupBy.quantile: args and quantiles differ in length")
         outs = [self._h.quantile(self.df.cols[self.df.names.index(nm)], [x], interpolation, skip_nulls, min_count)[0] for nm, x in zip(names, qs)]
         return DataFrame(dict(zip(names, outs)), index=uniq)
+
+    def mode(self, args):
+        """GroupBy::mode (src/group_by.h:126-127, src/dataframe.cpp:1808-1865): Arrow's mode with default options per group.  One column
+        name -> Series indexed by the unique keys; a list -> DataFrame with one <name> column per name, laid out as quantile's."""
+        uniq = self.unique()
+        if isinstance(args, str):
+            return Series(self._h.mode(self.df.cols[self.df.names.index(args)])[0], index=uniq, name=args)
+        names = list(args)
+        return DataFrame({nm: self._h.mode(self.df.cols[self.df.names.index(nm)])[0] for nm in names}, index=uniq)
 
     def min_max(self, args):
         """GroupBy::min_max (src/dataframe.cpp:1602-1696): arrow::compute::MinMax per group.  One column name -> frame with

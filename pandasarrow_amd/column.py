@@ -381,6 +381,71 @@ def quantile(a: Column, qs, interpolation=L.INTERP_LINEAR, skip_nulls=True, min_
     return res
 
 
+def mode(a: Column, n=1, skip_nulls=True, min_count=0):
+    """The min(n, distinct values) most frequent valid values of a column, by count descending then value ascending (pdx_mode: Arrow's
+    mode).  -> (modes Column of a's dtype, counts Column int64), both of the result's length (0: an empty result)."""
+    cap = max(0, min(int(n), a.length))
+    modes, counts = Column.empty(a.dtype, cap), Column.empty(L.INT64, cap)
+    mm, mc, ca = modes.mut(), counts.mut(), a.c()
+    L.check(L.load().pdx_mode(C.byref(ca), int(n), int(bool(skip_nulls)), int(min_count), C.byref(mm), C.byref(mc), _stream()))
+    return modes._adopt(mm), counts._adopt(mc)
+
+
+def mode_last_plan() -> dict:
+    """The path this thread's last pdx_mode took: {'path': 'count' | 'sort' | 'bool' | 'empty', 'bins': ..., 'width': ..., 'runs': ...}."""
+    buf = C.create_string_buffer(256)
+    L.check(L.load().pdx_mode_last_plan(buf, 256))
+    return dict(w.split("=", 1) for w in buf.value.decode().split() if "=" in w)
+
+
+_DTYPE_NAMES = {L.INT64: "int64", L.FLOAT64: "float64", L.BOOL: "bool", L.UINT64: "uint64", L.TIMESTAMP_NS: "timestamp[ns]", L.INT32: "int32",
+                L.FLOAT32: "float32"}
+
+
+def _frequency_key(a: Column, what) -> Column:
+    """the column as a group-by key: float64 as its bit pattern (distinct = distinct bits), bool as 0 / 1 (pdx_if_else)"""
+    if a.dtype in _NARROW:
+        raise L.PdxError(L.NOT_IMPLEMENTED, f"{what}: dtype {_DTYPE_NAMES[a.dtype]} is not supported (the group-by does not take 4-byte keys yet)")
+    if a.dtype == L.FLOAT64:
+        return Column(L.INT64, a.length, a.values, a.validity, a.offset, a.null_count)
+    if a.dtype == L.BOOL:
+        ones = Column(L.INT64, a.length, torch.ones(max(a.length, 1), dtype=torch.int64, device=_device()), None)
+        return if_else(a, ones, 0)
+    return a
+
+
+def value_counts(a: Column):
+    """The distinct values (distinct bit patterns; a null is one entry) in first-occurrence order and their row counts: pdx_groupby_create +
+    pdx_groupby_unique_keys + pdx_groupby_sizes.  -> (values Column of a's dtype, counts Column int64)."""
+    key = _frequency_key(a, "value_counts")
+    if a.length == 0:
+        return Column.empty(a.dtype, 0), Column.empty(L.INT64, 0)
+    h = GroupByHandle.create(key)
+    try:
+        u, counts = h.unique_keys(), h.sizes()
+    finally:
+        h.close()
+    nulls = u.length - int(aggregate(L.AGG_COUNT, u)[0])
+    validity = u.validity if nulls else None
+    if a.dtype == L.BOOL:  # (at most three entries)
+        hv, hok = u.to_numpy()
+        return Column.from_numpy(hv.astype(bool), None if not nulls else hok), counts
+    values = u.values.view(torch.float64) if a.dtype == L.FLOAT64 else u.values  # (the key was the bit pattern)
+    return Column(a.dtype, u.length, values, validity, u.offset, nulls), counts
+
+
+def is_unique(a: Column) -> bool:
+    """unique().size() == size(): a column with two nulls is not unique."""
+    key = _frequency_key(a, "is_unique")
+    if a.length == 0:
+        return True
+    h = GroupByHandle.create(key)
+    try:
+        return h.num_groups == a.length
+    finally:
+        h.close()
+
+
 # ---------------------------------------------------------------- filter / take / concat
 def _col_array(cols):
     arr = (L.PdxColumn * len(cols))(*[c.c() for c in cols])
@@ -753,6 +818,21 @@ class GroupByHandle:
         cv = values.c()
         L.check(L.load().pdx_groupby_quantile(self._h, C.byref(cv), qarr, len(qs), interp, int(bool(skip_nulls)), int(min_count), marr, _stream()))
         return [o._adopt(marr[i]) for i, o in enumerate(outs)]
+
+
+    def mode(self, values: Column):
+        """Per group the most frequent valid value (ties: the smallest) and its count (pdx_groupby_mode).  -> (modes, counts), G rows each."""
+        G = self.num_groups
+        modes, counts = Column.empty(values.dtype, G, with_validity=True), Column.empty(L.INT64, G)
+        mm, mc, cv = modes.mut(), counts.mut(), values.c()
+        L.check(L.load().pdx_groupby_mode(self._h, C.byref(cv), C.byref(mm), C.byref(mc), _stream()))
+        return modes._adopt(mm), counts._adopt(mc)
+
+    def sizes(self) -> Column:
+        """rows per group, group-id order (pdx_groupby_sizes)"""
+        out = Column.empty(L.INT64, self.num_groups)
+        L.check(L.load().pdx_groupby_sizes(self._h, out.values.data_ptr(), _stream()))
+        return out
 
 
 class GroupedValues:

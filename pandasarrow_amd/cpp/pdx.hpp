@@ -190,6 +190,12 @@ struct Scalar {
   }
 };
 
+// one entry of Series::mode: the value and how many rows hold it
+struct Mode {
+  Scalar mode;
+  int64_t count = 0;
+};
+
 // arrow::compute::QuantileOptions::Interpolation (pdx_interpolation)
 enum class Interpolation { LINEAR = PDX_INTERP_LINEAR, LOWER = PDX_INTERP_LOWER, HIGHER = PDX_INTERP_HIGHER, NEAREST = PDX_INTERP_NEAREST,
                            MIDPOINT = PDX_INTERP_MIDPOINT };
@@ -428,8 +434,54 @@ class Series {
     return Series(u, std::nullopt, m_name);
   }
   int64_t nunique() const { return unique().count().as<int64_t>(); }
+  // NDFrame::mode (src/ndframe.h:63-66, 255, src/ndframe.cpp:177-197): Arrow's mode -- the min(n, distinct) most frequent valid values, by
+  // count descending, ties by value ascending (NaN last); empty when Arrow's result is empty
+  std::vector<Mode> mode(int64_t n = 1, bool skip_nulls = true, uint32_t minCount = 0) const {
+    const int64_t cap = std::max<int64_t>(0, std::min<int64_t>(n, size()));
+    Array modes = Array::Empty(m_array.dtype, cap, false), counts = Array::Empty(PDX_INT64, cap, false);
+    auto c = m_array.c();
+    auto mm = modes.mut(), mc = counts.mut();
+    ThrowOnFailure(pdx_mode(&c, n, skip_nulls ? 1 : 0, (int64_t)minCount, &mm, &mc, nullptr));
+    modes.length = mm.length;
+    counts.length = mc.length;
+    const std::vector<int64_t> cv = counts.values_as<int64_t>();
+    const std::vector<double> fv = m_array.dtype == PDX_FLOAT64 ? modes.values_as<double>() : std::vector<double>();
+    const std::vector<int64_t> iv = m_array.dtype == PDX_FLOAT64 ? std::vector<int64_t>() : modes.values_as<int64_t>();
+    std::vector<Mode> out;
+    for (size_t i = 0; i < cv.size(); ++i) {
+      pdx_scalar v{};
+      v.dtype = m_array.dtype;
+      v.is_valid = 1;
+      v.count = cv[i];
+      if (m_array.dtype == PDX_FLOAT64) v.v.f64 = fv[i];
+      else v.v.i64 = iv[i];
+      out.push_back(Mode{Scalar(v), cv[i]});
+    }
+    return out;
+  }
+  // Series::value_counts (src/dataframe.cpp:1093-1100): the distinct values (distinct bit patterns; a null is one entry) in first-occurrence
+  // order and their counts -> frame with columns "values", "counts"
+  inline DataFrame value_counts() const;
+  // Series::is_unique (src/series.cpp:1243): unique().size() == size()
+  bool is_unique() const {
+    if (size() == 0) return true;
+    Array key = frequency_key();
+    auto ck = key.c();
+    pdx_groupby* h = nullptr;
+    ThrowOnFailure(pdx_groupby_create(&ck, nullptr, &h));
+    const int64_t G = pdx_groupby_num_groups(h);
+    pdx_groupby_destroy(h);
+    return G == size();
+  }
 
  private:
+  // the column as a group-by key: float64 as its bit pattern, bool as 0 / 1
+  Array frequency_key() const {
+    Array key = m_array;
+    if (m_array.dtype == PDX_FLOAT64) key.dtype = PDX_INT64;
+    else if (m_array.dtype == PDX_BOOL) key = run_if_else(m_array, Array::Make(std::vector<int64_t>((size_t)size(), 1)), Scalar((int64_t)0).to_array(), PDX_SCALAR_RHS);
+    return key;
+  }
   // (valid AND true, valid AND false) of a boolean Series; Arrow has no all / any kernel for other types, and min_count = 1
   std::pair<int64_t, int64_t> bool_counts(const char* what) const {
     if (m_array.dtype != PDX_BOOL) throw std::runtime_error(std::string("Function '") + what + "' has no kernel matching input types");
@@ -1450,6 +1502,23 @@ struct GroupBy {
     for (size_t i = 0; i < args.size(); ++i) cols.push_back(quantile_array(args[i], qs[i], interpolation, skip_nulls, min_count));
     return DataFrame(args, cols, unique());
   }
+  // GroupBy::mode (src/group_by.h:126-127, src/dataframe.cpp:1808-1865): Arrow's mode with default options over every group's rows (the most
+  // frequent valid value, ties to the smaller one); a group without a valid value is null.  Several names: one <name> column per name.
+  Array mode_array(const std::string& arg) const {
+    const Array& v = df.m_columns[(size_t)df.column_index(arg)];
+    Array out = Array::Empty(v.dtype, (int64_t)groupSize(), true), counts = Array::Empty(PDX_INT64, (int64_t)groupSize(), false);
+    auto c = v.c();
+    auto m = out.mut(), mc = counts.mut();
+    ThrowOnFailure(pdx_groupby_mode(handle->h, &c, &m, &mc, nullptr));
+    out.null_count = m.null_count;
+    return out;
+  }
+  Series mode(const std::string& arg) const { return Series(mode_array(arg), unique(), arg); }
+  DataFrame mode(const std::vector<std::string>& args) const {
+    std::vector<Array> cols;
+    for (auto& a : args) cols.push_back(mode_array(a));
+    return DataFrame(args, cols, unique());
+  }
 
   // ---- walking the groups (src/group_by.h:39-77; src/dataframe.cpp:1354-1510).  The reference materialises every group's arrays in
   // the constructor (Grouper::MakeGroupings + ApplyGroupings); here the groupings are built on first use (pdx_groupby_groupings) and a
@@ -1650,6 +1719,32 @@ inline Resampler DataFrame::downsample(const std::string& rule, bool closed_labe
   return Resampler(DataFrame(m_names, m_columns, binned), std::make_shared<GroupHandle>(h), PDX_TIMESTAMP_NS);
 }
 inline GroupBy DataFrame::group_by(const std::string& key) const { return GroupBy(key, *this); }
+inline DataFrame Series::value_counts() const {
+  if (size() == 0) return DataFrame({"values", "counts"}, {Array::Empty(m_array.dtype, 0, false), Array::Empty(PDX_INT64, 0, false)});
+  Array key = frequency_key();
+  auto ck = key.c();
+  pdx_groupby* h = nullptr;
+  ThrowOnFailure(pdx_groupby_create(&ck, nullptr, &h));
+  GroupHandle owner(h);
+  const int64_t G = pdx_groupby_num_groups(h);
+  Array u = Array::Empty(PDX_INT64, G, true), counts = Array::Empty(PDX_INT64, G, false);
+  auto mu = u.mut();
+  ThrowOnFailure(pdx_groupby_unique_keys(h, &mu, nullptr));
+  ThrowOnFailure(pdx_groupby_sizes(h, static_cast<int64_t*>(counts.values->ptr), nullptr));
+  pdx_scalar valid_rows{};
+  auto cu = u.c();
+  ThrowOnFailure(pdx_aggregate(PDX_AGG_COUNT, &cu, &valid_rows, nullptr));
+  u.null_count = G - valid_rows.v.i64;
+  if (u.null_count == 0) u.validity.reset();
+  if (m_array.dtype == PDX_BOOL) {  // (at most three entries)
+    const std::vector<int64_t> hv = u.values_as<int64_t>();
+    const std::vector<bool> ok = u.valid_flags();
+    u = Array::Make(std::vector<bool>(hv.begin(), hv.end()), u.null_count ? &ok : nullptr);
+  } else {
+    u.dtype = m_array.dtype;
+  }
+  return DataFrame({"values", "counts"}, {u, counts});
+}
 inline Resampler DataFrame::resample(const std::string& rule, bool cr, bool lr) const { return pd::resample(*this, rule, cr, lr); }
 inline Resampler Series::resample(const std::string& rule, bool cr, bool lr) const { return pd::resample(*this, rule_to_ns(rule), cr, lr); }
 

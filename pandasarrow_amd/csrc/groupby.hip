@@ -817,6 +817,51 @@ __global__ void k_iota_rows(uint32_t* __restrict__ p, int64_t n) {
 }
 }  // namespace pdx
 
+namespace pdx {
+// the rows of `gb` stably sorted by group id: *ks the sorted ids, *vs their rows (both n entries, living in `s`)
+static int sort_rows_by_group(pdx_groupby* gb, const uint32_t** ks, const uint32_t** vs, Scratch& s, void* stream, hipStream_t st) {
+  const int64_t n = gb->n, G = gb->G;
+  uint32_t* ids = s.get<uint32_t>((size_t)n);
+  uint32_t* rows = s.get<uint32_t>((size_t)n);
+  uint32_t* k0 = s.get<uint32_t>((size_t)n);
+  uint32_t* k1 = s.get<uint32_t>((size_t)n);
+  uint32_t* v0 = s.get<uint32_t>((size_t)n);
+  uint32_t* v1 = s.get<uint32_t>((size_t)n);
+  PDX_SCRATCH_CHECK(s);
+  PDX_TRY(pdx_groupby_group_ids(gb, ids, stream));
+  hipLaunchKernelGGL(k_iota_rows, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, rows, n);
+  PDX_LAUNCH_CHECK();
+  *ks = ids;
+  *vs = rows;
+  if (gb->mode == 0 && G > 1) {  // (segments mode: the rows are grouped as they stand)
+    const int bits = std::max(1, ilog2((uint64_t)G));
+    PDX_TRY((radix_sort_pairs<uint32_t>(ids, rows, k0, v0, k1, v1, n, bits, ks, vs, true, s, st)));
+  }
+  return PDX_OK;
+}
+__global__ void k_seg_sizes(const uint32_t* __restrict__ seg_start, int64_t G, long long* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += stride) out[g] = (long long)seg_start[g + 1] - (long long)seg_start[g];
+}
+// sizes[g] = the distance between the first positions of the ids g and g + 1 in the sorted ids
+__global__ void k_sorted_id_sizes(const uint32_t* __restrict__ sorted_ids, int64_t n, int64_t G, long long* __restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += stride) {
+    int64_t bound[2];
+    for (int k = 0; k < 2; ++k) {
+      int64_t lo = 0, hi = n;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)sorted_ids[mid] < g + k) lo = mid + 1;
+        else hi = mid;
+      }
+      bound[k] = lo;
+    }
+    out[g] = bound[1] - bound[0];
+  }
+}
+}  // namespace pdx
+
 extern "C" {
 // Grouper::MakeGroupings (src/dataframe.cpp:1546, 1562): the rows of every group, ascending, groups in group-id order
 int pdx_groupby_groupings(pdx_groupby* gb, int64_t* out_rows, int64_t* out_offsets, void* stream) {
@@ -830,24 +875,57 @@ int pdx_groupby_groupings(pdx_groupby* gb, int64_t* out_rows, int64_t* out_offse
     return PDX_OK;
   }
   Scratch s;
-  uint32_t* ids = s.get<uint32_t>((size_t)n);
-  uint32_t* rows = s.get<uint32_t>((size_t)n);
-  uint32_t* k0 = s.get<uint32_t>((size_t)n);
-  uint32_t* k1 = s.get<uint32_t>((size_t)n);
-  uint32_t* v0 = s.get<uint32_t>((size_t)n);
-  uint32_t* v1 = s.get<uint32_t>((size_t)n);
-  PDX_SCRATCH_CHECK(s);
-  PDX_TRY(pdx_groupby_group_ids(gb, ids, stream));
-  hipLaunchKernelGGL(k_iota_rows, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, rows, n);
-  PDX_LAUNCH_CHECK();
-  const uint32_t* ks = ids;
-  const uint32_t* vs = rows;
-  if (gb->mode == 0 && G > 1) {  // (segments mode: the rows are grouped as they stand)
-    const int bits = std::max(1, ilog2((uint64_t)G));
-    PDX_TRY((radix_sort_pairs<uint32_t>(ids, rows, k0, v0, k1, v1, n, bits, &ks, &vs, true, s, st)));
-  }
+  const uint32_t* ks = nullptr;
+  const uint32_t* vs = nullptr;
+  PDX_TRY(sort_rows_by_group(gb, &ks, &vs, s, stream, st));
   hipLaunchKernelGGL(k_groupings_finish, dim3(grid_for(n + G + 1, 256, 4)), dim3(256), 0, st, ks, vs, n, G, out_rows, out_offsets);
   PDX_LAUNCH_CHECK();
+  PDX_HIP(hipStreamSynchronize(st));
+  return PDX_OK;
+}
+
+// Rows per group, group-id order.  The handle keeps them once known (the COUNT of a column without nulls leaves them there and reads them
+// from there): from the segment boundaries (resample / downsample / sorted keys); else through that same COUNT -- the LDS accumulators of
+// gb_acc.hpp over the handle's slots, which reads no value column; else (few rows, or slots that do not fit LDS) from the rows sorted by
+// group id, as pdx_groupby_groupings sorts them.
+int pdx_groupby_sizes(pdx_groupby* gb, int64_t* out_sizes, void* stream) {
+  if (!gb || !out_sizes) return fail(PDX_INVALID, "pdx_groupby_sizes: null argument");
+  hipStream_t st = as_stream(stream);
+  gb->use_on(st);
+  const int64_t n = gb->n, G = gb->G;
+  if (G == 0) return PDX_OK;
+  Scratch s;
+  if (!gb->sizes_ready) {
+    long long* sizes = acc_sizes_cache(gb);
+    if (!sizes) return PDX_OOM;
+    const AccTuning at = AccTuning::read();
+    const AccGeom ag = acc_geometry(gb, false, kAccCnt, false, at);
+    if (gb->mode != 0 && gb->seg_start) {
+      hipLaunchKernelGGL(k_seg_sizes, dim3(grid_for(G, 256, 4)), dim3(256), 0, st, gb->seg_start, G, sizes);
+      PDX_LAUNCH_CHECK();
+      gb->sizes_ready = true;
+    } else if (ag.ok) {
+      pdx_column rows_only{};  // a column without nulls: COUNT touches the handle's slots alone, never the values
+      rows_only.dtype = PDX_INT64;
+      rows_only.length = n;
+      rows_only.values = gb->uniques;
+      SegOut oo{};
+      oo.count = s.get<long long>((size_t)G);
+      PDX_SCRATCH_CHECK(s);
+      PDX_TRY(reduce_acc(gb, ag, &rows_only, oo, nullptr, at, s, st, nullptr));  // (leaves the counts in gb->sizes)
+    } else if (n == 0) {
+      PDX_HIP(hipMemsetAsync(sizes, 0, (size_t)G * sizeof(long long), st));
+      gb->sizes_ready = true;
+    } else {
+      const uint32_t* ks = nullptr;
+      const uint32_t* vs = nullptr;
+      PDX_TRY(sort_rows_by_group(gb, &ks, &vs, s, stream, st));
+      hipLaunchKernelGGL(k_sorted_id_sizes, dim3(grid_for(G, 256)), dim3(256), 0, st, ks, n, G, sizes);
+      PDX_LAUNCH_CHECK();
+      gb->sizes_ready = true;
+    }
+  }
+  PDX_HIP(hipMemcpyAsync(out_sizes, gb->sizes, (size_t)G * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
   PDX_HIP(hipStreamSynchronize(st));
   return PDX_OK;
 }

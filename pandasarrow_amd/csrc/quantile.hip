@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <map>
 #include <vector>
+#include "group_order.hpp"
 #include "quantile.hpp"
 #include "radix_sort.hpp"
 
@@ -702,15 +703,6 @@ static int q_check_args(const char* what, const pdx_column* a, const double* q, 
 }
 
 // ---------------------------------------------------------------- group form
-__global__ void k_gq_gather(const unsigned long long* __restrict__ order, const uint32_t* __restrict__ gids, int64_t n, uint32_t* __restrict__ keys,
-                            uint32_t* __restrict__ rows) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint32_t r = (uint32_t)order[i];
-    rows[i] = r;
-    keys[i] = gids[r];
-  }
-}
 struct GQOuts {
   void* values[kQMaxTargets / 2];
   double q[kQMaxTargets / 2];
@@ -790,57 +782,17 @@ __global__ void __launch_bounds__(256) k_gq_pick(const T* __restrict__ v, const 
     }
   }
 }
-// ok bytes -> validity bits (+ the number of nulls)
-__global__ void k_gq_pack(const uint8_t* __restrict__ ok, int64_t G, uint8_t* __restrict__ bits, unsigned long long* __restrict__ nulls) {
-  const int64_t nbytes = (G + 7) >> 3, stride = (int64_t)gridDim.x * blockDim.x;
-  unsigned long long c = 0;
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nbytes; b += stride) {
-    unsigned byte = 0;
-    for (int j = 0; j < 8; ++j) {
-      const int64_t g = b * 8 + j;
-      if (g < G) {
-        if (ok[g]) byte |= 1u << j;
-        else ++c;
-      }
-    }
-    if (bits) bits[b] = (uint8_t)byte;
-  }
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(nulls, c);
-}
-
 template <typename T>
 static int groupby_quantile_typed(pdx_groupby* gb, const pdx_column* values, const double* q, int nq, int interp, int skip_nulls, int64_t min_count,
                                   pdx_mut_column* outs, void* stream, hipStream_t st) {
   const int64_t n = values->length, G = pdx_groupby_num_groups(gb);
   Scratch s;
-  unsigned long long* order = s.get<unsigned long long>((size_t)n);
-  uint32_t* gids = s.get<uint32_t>((size_t)n);
-  uint32_t* k0 = s.get<uint32_t>((size_t)n);
-  uint32_t* v0 = s.get<uint32_t>((size_t)n);
-  uint32_t* k1 = s.get<uint32_t>((size_t)n);
-  uint32_t* v1 = s.get<uint32_t>((size_t)n);
-  uint32_t* k2 = s.get<uint32_t>((size_t)n);
-  uint32_t* v2 = s.get<uint32_t>((size_t)n);
   uint8_t* ok = s.get<uint8_t>((size_t)G * (size_t)nq);
   unsigned long long* nulls = s.get<unsigned long long>((size_t)nq);
   PDX_SCRATCH_CHECK(s);
-  pdx_mut_column om{};
-  om.dtype = PDX_UINT64;
-  om.length = n;
-  om.values = order;
-  PDX_TRY(pdx_argsort(values, 1, &om, stream));
-  PDX_TRY(pdx_groupby_group_ids(gb, gids, stream));
-  note_stream(st);
-  hipLaunchKernelGGL(k_gq_gather, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, order, gids, n, k0, v0);
-  PDX_LAUNCH_CHECK();
-  const uint32_t* ks = k0;
-  const uint32_t* vs = v0;
-  if (G > 1) {
-    int bits = 1;
-    while (bits < 32 && ((uint64_t)(G - 1) >> bits)) ++bits;
-    PDX_TRY((radix_sort_pairs<uint32_t>(k0, v0, k1, v1, k2, v2, n, bits, &ks, &vs, true, s, st)));
-  }
+  const uint32_t* ks = nullptr;
+  const uint32_t* vs = nullptr;
+  PDX_TRY(build_group_value_order(gb, values, &ks, &vs, s, stream, st));
   PDX_HIP(hipMemsetAsync(nulls, 0, sizeof(unsigned long long) * (size_t)nq, st));
   const T* v = static_cast<const T*>(values->values) + values->offset;
   const uint8_t* valid = validity_or_null(values);
@@ -855,7 +807,7 @@ static int groupby_quantile_typed(pdx_groupby* gb, const pdx_column* values, con
                        ok + (size_t)k0i * (size_t)G);
   }
   for (int k = 0; k < nq; ++k)
-    hipLaunchKernelGGL(k_gq_pack, dim3(grid_for((G + 7) / 8, 256)), dim3(256), 0, st, ok + (size_t)k * (size_t)G, G, static_cast<uint8_t*>(outs[k].validity),
+    hipLaunchKernelGGL(k_go_pack, dim3(grid_for((G + 7) / 8, 256)), dim3(256), 0, st, ok + (size_t)k * (size_t)G, G, static_cast<uint8_t*>(outs[k].validity),
                        nulls + k);
   PDX_LAUNCH_CHECK();
   std::vector<unsigned long long> hn((size_t)nq);

@@ -7,6 +7,7 @@
 // (Arrow 25.0.0 behaviour, pinned by tests/golden agg_i64_*); min/max skip NaN unless all values are NaN and keep
 // the FIRST of tied values (0.0 vs -0.0), implemented as an order-independent (value, row) reduction.
 #include <string.h>
+#include "colview.hpp"
 #include "minmax.hpp"
 #include "pairwise.hpp"
 #include "scan.hpp"
@@ -19,15 +20,6 @@ constexpr int kLeafPad = 17;                    // LDS stride per leaf (doubles)
 
 template <typename T>
 __device__ __forceinline__ double to_f64(T x) { return (double)x; }
-
-// small device-to-host read (<= 64 bytes) through this thread's pinned slot: a copy into pageable memory is staged by the runtime
-static int read_back(void* dst, const void* dev, size_t bytes, hipStream_t st) {
-  void* pin = bytes <= 64 ? pinned_slot() : nullptr;
-  PDX_HIP(hipMemcpyAsync(pin ? pin : dst, dev, bytes, hipMemcpyDeviceToHost, st));
-  PDX_HIP(hipStreamSynchronize(st));
-  if (pin) memcpy(dst, pin, bytes);
-  return PDX_OK;
-}
 
 // ---------------------------------------------------------------- dense path, level 0
 // block b: values [4096b, 4096b+4096) -> 256 leaf sums -> full block: one level-8 node, ragged last block: raw leaves

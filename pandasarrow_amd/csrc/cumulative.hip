@@ -1,10 +1,12 @@
 // cumulative.hip -- pdx_cumulative (cumsum / cumprod / cummax / cummin), pdx_fill_null (ffill / bfill), pdx_shift.
-// The scans are cum_scan.hpp's Scan<T, Op>; shift is one pass of its own (a row per lane, validity by ballot).
+// The scans are cum_scan.hpp's Scan<T, Op>; shift is one pass of its own (a row per lane, validity by ballot).  The null counter, its
+// read-back and the wave's null count are colview.hpp's.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include "colview.hpp"
 #include "cum_scan.hpp"
 
 namespace pdx {
@@ -20,18 +22,6 @@ static int64_t scan_chunk_tiles() {
   return env_rows > 0 ? ceil_div(env_rows, kCumTile) : 0;
 }
 
-static int read_nulls(const unsigned long long* dev, int64_t* out, hipStream_t st) {
-  unsigned long long h = 0;
-  void* pin = pinned_slot();
-  PDX_HIP(hipMemcpyAsync(pin ? pin : &h, dev, sizeof(h), hipMemcpyDeviceToHost, st));
-  PDX_HIP(hipStreamSynchronize(st));
-  if (pin) memcpy(&h, pin, sizeof(h));
-  *out = (int64_t)h;
-  return PDX_OK;
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // the checks the three entry points share
 static int check_io(const pdx_column* a, const pdx_mut_column* out, const char* who, bool timestamp_ok) {
   PDX_TRY(check_column(a, who, true));
@@ -42,16 +32,6 @@ static int check_io(const pdx_column* a, const pdx_mut_column* out, const char* 
   if (out->dtype != dt || out->length < a->length) return fail(PDX_INVALID, std::string(who) + ": output dtype / length do not match the input");
   if (a->length > 0 && !out->values) return fail(PDX_INVALID, std::string(who) + ": null output buffer");
   if (a->length > 0 && out->values == a->values) return fail(PDX_INVALID, std::string(who) + ": in-place operation (out aliases the input) is not supported");
-  return PDX_OK;
-}
-
-// the device word that counts the null rows of the output: only an output with a bitmap has one
-static int open_null_count(const pdx_mut_column* out, Scratch& s, hipStream_t st, unsigned long long** nulls) {
-  *nulls = nullptr;
-  if (!out->validity) return PDX_OK;
-  *nulls = s.get<unsigned long long>(1);
-  PDX_SCRATCH_CHECK(s);
-  PDX_HIP(hipMemsetAsync(*nulls, 0, sizeof(**nulls), st));
   return PDX_OK;
 }
 
@@ -125,15 +105,12 @@ __global__ void __launch_bounds__(256) k_shift(const T* __restrict__ in, const u
       ok = from_a ? (!valid || bit_get(valid, voff + s)) : fill_valid != 0;
     }
     if (ovalid) {
-      const unsigned long long word = __ballot(ok);
+      const unsigned long long word = __ballot(ok);  // (the last byte is written whole: not colview.hpp's tail-preserving store)
       if (lane < 8 && (w << 6) + lane * 8 < n) ovalid[(w << 3) + lane] = (uint8_t)(word >> (8 * lane));
       if (in_out && !ok) ++nc;
     }
   }
-  if (ovalid) {
-    for (int d = 32; d > 0; d >>= 1) nc += __shfl_down(nc, d, 64);
-    if (lane == 0 && nc) atomicAdd(nulls, nc);
-  }
+  if (ovalid) wave_add_nulls(nulls, lane, nc);
 }
 
 }  // namespace pdx
@@ -168,7 +145,7 @@ int pdx_cumulative(int op, const pdx_column* a, double start, int skip_nulls, pd
   if (n == 0) return PDX_OK;
   Scratch s;
   unsigned long long* nulls = nullptr;
-  PDX_TRY(open_null_count(out, s, st, &nulls));
+  if (out->validity) PDX_TRY(open_null_counter(s, st, &nulls));  // only an output with a bitmap has a counter
   const int skip = skip_nulls != 0;
   switch (a->dtype) {
     case PDX_INT64: PDX_TRY(run_cumulative_op<int64_t>(op, a, si, skip, out, nulls, s, st)); break;
@@ -177,7 +154,7 @@ int pdx_cumulative(int op, const pdx_column* a, double start, int skip_nulls, pd
     case PDX_FLOAT32: PDX_TRY(run_cumulative_op<float>(op, a, (float)start, skip, out, nulls, s, st)); break;
     default: PDX_TRY(run_cumulative_op<double>(op, a, start, skip, out, nulls, s, st)); break;
   }
-  if (has_nulls) PDX_TRY(read_nulls(nulls, &out->null_count, st));  // the one case that synchronises
+  if (has_nulls) PDX_TRY(read_back(&out->null_count, nulls, sizeof(out->null_count), st));  // the one case that synchronises
   return PDX_OK;
 }
 
@@ -193,11 +170,11 @@ int pdx_fill_null(int backward, const pdx_column* a, pdx_mut_column* out, void* 
   if (n == 0) return PDX_OK;
   Scratch s;
   unsigned long long* nulls = nullptr;
-  PDX_TRY(open_null_count(out, s, st, &nulls));
+  if (out->validity) PDX_TRY(open_null_counter(s, st, &nulls));  // only an output with a bitmap has a counter
   const CumArgs c = scan_args(a, out, backward != 0, 0, nulls);
   if (dtype_bytes(a->dtype) == 4) PDX_TRY((cum_scan_launch<uint32_t, CumLatest>(c, CumElem<uint32_t>{0u, 0}, scan_chunk_tiles(), s, st)));
   else PDX_TRY((cum_scan_launch<uint64_t, CumLatest>(c, CumElem<uint64_t>{0ull, 0}, scan_chunk_tiles(), s, st)));
-  if (has_nulls) PDX_TRY(read_nulls(nulls, &out->null_count, st));
+  if (has_nulls) PDX_TRY(read_back(&out->null_count, nulls, sizeof(out->null_count), st));
   return PDX_OK;
 }
 
@@ -219,7 +196,7 @@ int pdx_shift(const pdx_column* a, int64_t periods, const pdx_scalar* fill, pdx_
   if (n == 0) return PDX_OK;
   Scratch s;
   unsigned long long* nulls = nullptr;
-  PDX_TRY(open_null_count(out, s, st, &nulls));
+  if (out->validity) PDX_TRY(open_null_counter(s, st, &nulls));  // only an output with a bitmap has a counter
   const int64_t p = periods > n ? n : periods < -n ? -n : periods;  // |periods| >= length: a column of fills
   const dim3 grid(grid_for(n, 256, 4)), block(256);
   uint8_t* ov = static_cast<uint8_t*>(out->validity);
@@ -242,7 +219,7 @@ int pdx_shift(const pdx_column* a, int64_t periods, const pdx_scalar* fill, pdx_
   PDX_LAUNCH_CHECK();
   // known on the host unless rows of a column with nulls are kept: only then does the call synchronise
   if (fills == n || !has_nulls) out->null_count = fill_valid ? 0 : fills;
-  else PDX_TRY(read_nulls(nulls, &out->null_count, st));
+  else PDX_TRY(read_back(&out->null_count, nulls, sizeof(out->null_count), st));
   return PDX_OK;
 }
 

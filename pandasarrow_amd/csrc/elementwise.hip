@@ -13,7 +13,7 @@
 // time.
 #include <limits>
 #include <type_traits>
-#include "pdx_common.hpp"
+#include "colview.hpp"
 
 namespace pdx {
 
@@ -475,7 +475,6 @@ static int with_num_type(int dt, F&& f) {
     default: return f(double{});
   }
 }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static int result_dt(int da, int db) {
   return with_num_type(da, [&](auto ta) { return with_num_type(db, [&](auto tb) { return dt_of<typename Promote<decltype(ta), decltype(tb)>::type>(); }); });
 }

@@ -21,6 +21,7 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
+#include "colview.hpp"
 #include "compact.hpp"
 #include "group_order.hpp"
 #include "minmax.hpp"
@@ -258,12 +259,6 @@ __global__ void k_mode_emit(const T* __restrict__ v, const unsigned long long* _
   }
 }
 
-static int mode_copy_sync(void* dst, const void* src, size_t bytes, hipStream_t st) {
-  PDX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-  PDX_HIP(hipStreamSynchronize(st));
-  return PDX_OK;
-}
-
 static void mode_done(pdx_mut_column* out_modes, pdx_mut_column* out_counts, int64_t k) {
   out_modes->length = out_counts->length = k;
   out_modes->null_count = out_counts->null_count = 0;
@@ -279,7 +274,7 @@ static int mode_top_emit(const T* v, const unsigned long long* order, const uint
   hipLaunchKernelGGL(k_mode_top, dim3(grid_for(R, 256, 4)), dim3(256), 0, st, cnt, R, res);
   PDX_LAUNCH_CHECK();
   unsigned long long hres[2];
-  PDX_TRY(mode_copy_sync(hres, res, sizeof(hres), st));
+  PDX_TRY(read_back(hres, res, sizeof(hres), st));
   const int64_t k = std::min<int64_t>(n_want, (int64_t)hres[1]);
   if (k <= 0) return fail(PDX_DEVICE, "pdx_mode: no candidate although a valid row exists");
   const uint32_t maxc = (uint32_t)(hres[0] >> 32);
@@ -322,7 +317,7 @@ static int mode_typed(const pdx_column* a, int64_t n_want, int skip_nulls, int64
   hipLaunchKernelGGL(k_mode_scan<T>, dim3(grid), dim3(kModeBlock), 0, st, v, valid, a->offset, n, part);
   PDX_LAUNCH_CHECK();
   std::vector<ModeScan> hp((size_t)grid);
-  PDX_TRY(mode_copy_sync(hp.data(), part, sizeof(ModeScan) * (size_t)grid, st));
+  PDX_TRY(read_back(hp.data(), part, sizeof(ModeScan) * (size_t)grid, st));
   unsigned long long kmin = ~0ull, kmax = 0;
   int64_t V = 0;
   bool any = false;
@@ -387,7 +382,7 @@ static int mode_bool(const pdx_column* a, int64_t n_want, int skip_nulls, int64_
                      a->offset, n, res);
   PDX_LAUNCH_CHECK();
   unsigned long long h[2];
-  PDX_TRY(mode_copy_sync(h, res, sizeof(h), st));
+  PDX_TRY(read_back(h, res, sizeof(h), st));
   const int64_t V = (int64_t)h[1], t = (int64_t)h[0], f = V - t;
   if (V == 0 || V < min_count || (!skip_nulls && V < n)) {
     g_mode_plan = "path=empty";
@@ -475,7 +470,7 @@ static int groupby_mode_typed(pdx_groupby* gb, const pdx_column* values, pdx_mut
   hipLaunchKernelGGL(k_go_pack, dim3(grid_for((G + 7) / 8, 256)), dim3(256), 0, st, ok, G, static_cast<uint8_t*>(out_modes->validity), nulls);
   PDX_LAUNCH_CHECK();
   unsigned long long hn = 0;
-  PDX_TRY(mode_copy_sync(&hn, nulls, sizeof(hn), st));
+  PDX_TRY(read_back(&hn, nulls, sizeof(hn), st));
   if (hn && !out_modes->validity) {  // (known only now: the rows have been written, so the outputs are handed back empty)
     out_modes->length = out_counts->length = 0;
     out_modes->null_count = out_counts->null_count = -1;

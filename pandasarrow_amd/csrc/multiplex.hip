@@ -9,7 +9,7 @@
 //   Series::indices_nonzero                     : "indices_nonzero"                                      src/series.cpp:365
 //
 // Shapes.  coalesce and min / max: a lane owns a row (four consecutive rows of a 4-byte coalesce whose streams start on 16 bytes), a wave
-// 64 (256) consecutive rows; the columns come as a device table read with uniform loads, as the 64-bit validity words are.  coalesce keeps
+// 64 (256) consecutive rows; the columns come as a device table (colview.hpp's ColView) read with uniform loads, as the 64-bit validity words are.  coalesce keeps
 // the rows of its words that still lack a value as wave-uniform masks: a column is loaded only by the lanes it gives a value to, and the
 // column loop ends when no row is pending -- a frame whose first column is mostly valid moves about one column.  clip folds both levels
 // of the nesting over one read of x.  replace_with_mask is compact.hpp's two passes: valid-true mask rows per tile, scanned, then a pass
@@ -19,64 +19,13 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+#include "colview.hpp"
 #include "compact.hpp"
 
 namespace pdx {
 
-constexpr int kMxMaxCols = 2046;  // as pdx_row_aggregate
+constexpr int kMxMaxCols = 2046;  // as pdx_row_aggregate (row_aggregate.hip's kRowMaxCols)
 constexpr int kMxU = 4;           // column loads in flight per lane
-
-struct MxCol {
-  const void* values;    // element offset applied (PDX_BOOL: the bitmap's base)
-  const uint8_t* valid;  // nullptr: every row is valid
-  int64_t voff;          // bit offset into valid
-  int64_t boff;          // PDX_BOOL: bit offset into values
-};
-
-// 64 bits starting at bit `bitpos` of `bits`, of which the caller uses the first `nbits` (>= 1): two aligned 64-bit words and a funnel
-// shift.  Every word read holds at least one byte of the `nbits` asked for, so no read leaves the pages of the bitmap.  All operands
-// are wave-uniform: the loads are scalar.
-__device__ __forceinline__ uint64_t mx_bits64(const uint8_t* bits, int64_t bitpos, int nbits) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(bits) + (uintptr_t)(bitpos >> 3);
-  const __attribute__((address_space(4))) uint64_t* p = (const __attribute__((address_space(4))) uint64_t*)(a & ~(uintptr_t)7);
-  const int sh = (int)(a & 7) * 8 + (int)(bitpos & 7);
-  uint64_t r = p[0] >> sh;
-  if (sh + nbits > 64) r |= p[1] << (64 - sh);
-  return r;
-}
-// word w of a bit-packed output, a wave's store: lanes 0..7 write a byte each; the byte that holds row n keeps its bits from n on
-__device__ __forceinline__ void mx_store_bits(uint8_t* dst, int64_t w, int64_t n, uint64_t word, int lane) {
-  if (lane >= 8) return;
-  const int64_t r0 = (w << 6) + lane * 8;
-  if (r0 >= n) return;
-  uint8_t b = (uint8_t)(word >> (8 * lane));
-  const int64_t rem = n - r0;
-  if (rem < 8) {
-    const uint8_t m = (uint8_t)((1u << rem) - 1u);
-    b = (uint8_t)((dst[(w << 3) + lane] & ~m) | (b & m));
-  }
-  dst[(w << 3) + lane] = b;
-}
-// the same for a thread that owns the word
-__device__ __forceinline__ void mx_store_word(uint8_t* dst, int64_t w, int64_t n, uint64_t word) {
-  const int64_t rem = n - (w << 6);
-  if (rem >= 64) {
-    reinterpret_cast<uint64_t*>(dst)[w] = word;
-    return;
-  }
-  const int nbytes = (int)((rem + 7) >> 3);
-  for (int q = 0; q < nbytes; ++q) {
-    uint8_t b = (uint8_t)(word >> (8 * q));
-    if (q == nbytes - 1 && (rem & 7)) {
-      const uint8_t m = (uint8_t)((1u << (rem & 7)) - 1u);
-      b = (uint8_t)((dst[(w << 3) + q] & ~m) | (b & m));
-    }
-    dst[(w << 3) + q] = b;
-  }
-}
-__device__ __forceinline__ int mx_first_wave() { return __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)); }
-// the first min(rem, 64) bits set (none for rem <= 0)
-__device__ __forceinline__ uint64_t mx_in_range(int64_t rem) { return rem >= 64 ? ~0ull : rem > 0 ? (1ull << rem) - 1ull : 0ull; }
 
 template <typename B>
 using MxV4 = B __attribute__((ext_vector_type(4)));  // 16 bytes of a 4-byte stream
@@ -97,13 +46,13 @@ __device__ __forceinline__ uint32_t mx_lane_bits(const uint64_t (&w)[R], int lan
 // pend: the rows of the wave's words that no column has given a value yet.  A column takes `pend & its validity word`; only the lanes
 // with a bit there load from it.  Values travel as bits (B = uint32_t / uint64_t), so NaN payloads and -0.0 survive.
 template <typename B, int R>
-__global__ void __launch_bounds__(256) k_coalesce(const MxCol* __restrict__ tab, int ncols, int64_t n, B* __restrict__ out, uint8_t* __restrict__ ovalid,
+__global__ void __launch_bounds__(256) k_coalesce(const ColView* __restrict__ tab, int ncols, int64_t n, B* __restrict__ out, uint8_t* __restrict__ ovalid,
                                                   unsigned long long* __restrict__ nulls) {
   const int lane = threadIdx.x & 63;
   constexpr int64_t kRows = 64 * R;
   const int64_t ngroups = (n + kRows - 1) / kRows, nwaves = (int64_t)(gridDim.x * blockDim.x) >> 6;
   unsigned long long nc = 0;  // (wave-uniform)
-  for (int64_t g = mx_first_wave(); g < ngroups; g += nwaves) {
+  for (int64_t g = first_word_of_wave(); g < ngroups; g += nwaves) {
     const int64_t base = g * kRows;
     const bool full = base + kRows <= n;
     uint64_t inr[R], pend[R];
@@ -112,7 +61,7 @@ __global__ void __launch_bounds__(256) k_coalesce(const MxCol* __restrict__ tab,
     for (int j = 0; j < R; ++j) {
       const int64_t rem = n - (base + 64 * j);
       nbits[j] = rem >= 64 ? 64 : rem > 0 ? (int)rem : 0;
-      inr[j] = mx_in_range(rem);
+      inr[j] = in_range_mask(rem);
       pend[j] = inr[j];
     }
     B val[R];
@@ -127,11 +76,11 @@ __global__ void __launch_bounds__(256) k_coalesce(const MxCol* __restrict__ tab,
 #pragma unroll
         for (int k = 0; k < R; ++k) v[u][k] = B(0);
         if (c0 + u < ncols) {
-          const MxCol e = tab[c0 + u];
+          const ColView e = tab[c0 + u];
           uint64_t take[R];
 #pragma unroll
           for (int j = 0; j < R; ++j) {
-            const uint64_t vw = !nbits[j] ? 0ull : e.valid ? mx_bits64(e.valid, e.voff + base + 64 * j, nbits[j]) : ~0ull;
+            const uint64_t vw = !nbits[j] ? 0ull : e.valid ? load_bits64_uniform(e.valid, e.voff + base + 64 * j, nbits[j]) : ~0ull;
             take[j] = pend[j] & vw;
             pend[j] &= ~vw;
           }
@@ -181,35 +130,33 @@ __global__ void __launch_bounds__(256) k_coalesce(const MxCol* __restrict__ tab,
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       if (!nbits[j]) continue;
-      if (ovalid) mx_store_bits(ovalid, g * R + j, n, inr[j] & ~pend[j], lane);
+      if (ovalid) store_bits_wave(ovalid, g * R + j, n, inr[j] & ~pend[j], lane);
       nc += (unsigned long long)__popcll(pend[j]);
     }
   }
   if (nulls && lane == 0 && nc) atomicAdd(nulls, nc);
 }
 // bit-packed cells: a thread owns a 64-row word of every column
-__global__ void __launch_bounds__(256) k_coalesce_bool(const MxCol* __restrict__ tab, int ncols, int64_t n, uint8_t* __restrict__ out, uint8_t* __restrict__ ovalid,
+__global__ void __launch_bounds__(256) k_coalesce_bool(const ColView* __restrict__ tab, int ncols, int64_t n, uint8_t* __restrict__ out, uint8_t* __restrict__ ovalid,
                                                        unsigned long long* __restrict__ nulls) {
   const int64_t nwords = (n + 63) >> 6, stride = (int64_t)gridDim.x * blockDim.x;
   unsigned long long nc = 0;
   for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += stride) {
     const int64_t base = w << 6;
-    const uint64_t inr = mx_in_range(n - base);
+    const uint64_t inr = in_range_mask(n - base);
     uint64_t pend = inr, val = 0;
     for (int c = 0; c < ncols && pend; ++c) {
-      const MxCol e = tab[c];
+      const ColView e = tab[c];
       const uint64_t vw = e.valid ? load_bits64(e.valid, e.voff + base, e.voff + n) : ~0ull;
       const uint64_t take = pend & vw;
       if (take) val |= take & load_bits64(static_cast<const uint8_t*>(e.values), e.boff + base, e.boff + n);
       pend &= ~vw;
     }
-    mx_store_word(out, w, n, val);
-    if (ovalid) mx_store_word(ovalid, w, n, inr & ~pend);
+    store_bits_word(out, w, n, val);
+    if (ovalid) store_bits_word(ovalid, w, n, inr & ~pend);
     nc += (unsigned long long)__popcll(pend);
   }
-  if (!nulls) return;
-  for (int d = 32; d > 0; d >>= 1) nc += __shfl_down(nc, d, 64);
-  if ((threadIdx.x & 63) == 0 && nc) atomicAdd(nulls, nc);
+  if (nulls) wave_add_nulls(nulls, threadIdx.x & 63, nc);
 }
 
 // ---------------------------------------------------------------- min_element_wise / max_element_wise, clip
@@ -263,7 +210,7 @@ struct MxAcc {
 // tab: the nscalar broadcast operands (one value each), then the arrays.  CLIP: tab = {x, hi, lo}: max(min(x, hi), lo), each level with
 // the options on its own, over one read of x.
 template <typename T, bool CLIP>
-__global__ void __launch_bounds__(256) k_minmax(const MxCol* __restrict__ tab, int nscalar, int ncols, int64_t n, int is_max_i, int skip_i, T* __restrict__ out,
+__global__ void __launch_bounds__(256) k_minmax(const ColView* __restrict__ tab, int nscalar, int ncols, int64_t n, int is_max_i, int skip_i, T* __restrict__ out,
                                                 uint8_t* __restrict__ ovalid, unsigned long long* __restrict__ nulls) {
   const int lane = threadIdx.x & 63;
   const bool is_max = is_max_i != 0, skip = skip_i != 0;
@@ -273,28 +220,28 @@ __global__ void __launch_bounds__(256) k_minmax(const MxCol* __restrict__ tab, i
   T hi = T(0), lo = T(0);
   bool hi_ok = false, lo_ok = false;
   if constexpr (CLIP) {
-    const MxCol eh = tab[1], el = tab[2];
+    const ColView eh = tab[1], el = tab[2];
     hi = static_cast<const T*>(eh.values)[0];
     lo = static_cast<const T*>(el.values)[0];
     hi_ok = !eh.valid || bit_get(eh.valid, eh.voff);
     lo_ok = !el.valid || bit_get(el.valid, el.voff);
   } else {
     for (int s = 0; s < nscalar; ++s) {
-      const MxCol e = tab[s];
+      const ColView e = tab[s];
       s0.scalar(is_max, static_cast<const T*>(e.values)[0], !e.valid || bit_get(e.valid, e.voff));
     }
   }
   unsigned long long nc = 0;
-  for (int64_t w = mx_first_wave(); w < nwords; w += nwaves) {
+  for (int64_t w = first_word_of_wave(); w < nwords; w += nwaves) {
     const int64_t base = w << 6, i = base + lane;
     const bool in = i < n;
     const int nbits = n - base < 64 ? (int)(n - base) : 64;
-    const uint64_t inr = mx_in_range(nbits);
+    const uint64_t inr = in_range_mask(nbits);
     T r;
     bool ok;
     if constexpr (CLIP) {
-      const MxCol e = tab[0];
-      const uint64_t vw = e.valid ? mx_bits64(e.valid, e.voff + base, nbits) : ~0ull;
+      const ColView e = tab[0];
+      const uint64_t vw = e.valid ? load_bits64_uniform(e.valid, e.voff + base, nbits) : ~0ull;
       const T x = in ? ((const __attribute__((address_space(1))) T*)e.values)[i] : T(0);
       MxAcc<T> a, b;
       a.init();
@@ -316,8 +263,8 @@ __global__ void __launch_bounds__(256) k_minmax(const MxCol* __restrict__ tab, i
           v[u] = T(0);
           vw[u] = 0;
           if (c0 + u < ncols) {
-            const MxCol e = tab[c0 + u];
-            vw[u] = e.valid ? mx_bits64(e.valid, e.voff + base, nbits) : ~0ull;
+            const ColView e = tab[c0 + u];
+            vw[u] = e.valid ? load_bits64_uniform(e.valid, e.voff + base, nbits) : ~0ull;
             if (in) v[u] = ((const __attribute__((address_space(1))) T*)e.values)[i];
           }
         }
@@ -330,13 +277,11 @@ __global__ void __launch_bounds__(256) k_minmax(const MxCol* __restrict__ tab, i
     }
     if (in) out[i] = ok ? r : T(0);
     if (ovalid) {
-      mx_store_bits(ovalid, w, n, __ballot(ok), lane);
+      store_bits_wave(ovalid, w, n, __ballot(ok), lane);
       if (in && !ok) ++nc;
     }
   }
-  if (!nulls) return;
-  for (int d = 32; d > 0; d >>= 1) nc += __shfl_down(nc, d, 64);
-  if (lane == 0 && nc) atomicAdd(nulls, nc);
+  if (nulls) wave_add_nulls(nulls, lane, nc);
 }
 
 // ---------------------------------------------------------------- replace_with_mask
@@ -369,8 +314,8 @@ __global__ void __launch_bounds__(kCompactBlock) k_replace_with_mask(RwmArgs p, 
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t base = (int64_t)blockIdx.x * kCompactTile + wave * (64 * kCompactItems);
   auto hits_of = [&](int64_t i0, int nb, uint64_t& mv) -> uint64_t {
-    mv = (p.mvalid ? mx_bits64(p.mvalid, p.moff + i0, nb) : ~0ull) & mx_in_range(nb);
-    return mx_bits64(p.mask, p.moff + i0, nb) & mv;
+    mv = (p.mvalid ? load_bits64_uniform(p.mvalid, p.moff + i0, nb) : ~0ull) & in_range_mask(nb);
+    return load_bits64_uniform(p.mask, p.moff + i0, nb) & mv;
   };
   int cnt = 0;
   for (int s = 0; s < kCompactItems; ++s) {
@@ -391,22 +336,22 @@ __global__ void __launch_bounds__(kCompactBlock) k_replace_with_mask(RwmArgs p, 
     const int nb = p.n - i0 < 64 ? (int)(p.n - i0) : 64;
     uint64_t mv;
     const uint64_t hit = hits_of(i0, nb, mv);
-    const uint64_t keep_ok = (p.avalid ? mx_bits64(p.avalid, p.aoff + i0, nb) : ~0ull) & mv;
+    const uint64_t keep_ok = (p.avalid ? load_bits64_uniform(p.avalid, p.aoff + i0, nb) : ~0ull) & mv;
     const int64_t i = i0 + lane;
     const bool in = lane < nb, mine = (hit >> lane) & 1ull;
     const int64_t k = pos + __popcll(hit & lt);
     const bool kin = mine && k < p.rlen;
     const bool ok = in && (mine ? (kin && (!p.rvalid || bit_get(p.rvalid, p.roff + k))) : (bool)((keep_ok >> lane) & 1ull));
     if constexpr (BOOL) {
-      const uint64_t abits = mx_bits64(static_cast<const uint8_t*>(p.a), p.aoff + i0, nb);
+      const uint64_t abits = load_bits64_uniform(static_cast<const uint8_t*>(p.a), p.aoff + i0, nb);
       const bool bit = mine ? (kin && bit_get(static_cast<const uint8_t*>(p.repl), p.roff + k)) : (bool)((abits >> lane) & 1ull);
-      mx_store_bits(static_cast<uint8_t*>(p.out), i0 >> 6, p.n, __ballot(ok && bit), lane);
+      store_bits_wave(static_cast<uint8_t*>(p.out), i0 >> 6, p.n, __ballot(ok && bit), lane);
     } else {
       B v = B(0);
       if (ok) v = mine ? static_cast<const B*>(p.repl)[k] : static_cast<const B*>(p.a)[i];
       if (in) static_cast<B*>(p.out)[i] = v;
     }
-    if (p.ovalid) mx_store_bits(p.ovalid, i0 >> 6, p.n, __ballot(ok), lane);
+    if (p.ovalid) store_bits_wave(p.ovalid, i0 >> 6, p.n, __ballot(ok), lane);
     nc += (unsigned int)(nb - __popcll(__ballot(ok)));
     pos += __popcll(hit);
   }
@@ -439,67 +384,21 @@ struct RowIdEmit {
 };
 
 // ---------------------------------------------------------------- all_valid_mask: tab holds the columns that bring a bitmap
-__global__ void __launch_bounds__(256) k_all_valid(const MxCol* __restrict__ tab, int ncols, int64_t n, uint8_t* __restrict__ out) {
+__global__ void __launch_bounds__(256) k_all_valid(const ColView* __restrict__ tab, int ncols, int64_t n, uint8_t* __restrict__ out) {
   const int64_t nwords = (n + 63) >> 6, stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += stride) {
     const int64_t base = w << 6;
-    uint64_t r = mx_in_range(n - base);
+    uint64_t r = in_range_mask(n - base);
     for (int c = 0; c < ncols; ++c) r &= load_bits64(tab[c].valid, tab[c].voff + base, tab[c].voff + n);
-    mx_store_word(out, w, n, r);
+    store_bits_word(out, w, n, r);
   }
 }
 
 // ---------------------------------------------------------------- host side
-static const char* mx_arrow_name(int dt) {
-  switch (dt) {
-    case PDX_FLOAT64: return "double";
-    case PDX_FLOAT32: return "float";
-    default: return dtype_name(dt);
-  }
-}
 static bool mx_known_dtype(int dt) { return dt >= PDX_INT64 && dt <= PDX_FLOAT32; }
-static MxCol mx_entry(const pdx_column& a) {
-  MxCol e;
-  e.values = a.dtype == PDX_BOOL ? a.values : static_cast<const void*>(static_cast<const char*>(a.values) + (size_t)a.offset * (size_t)dtype_bytes(a.dtype));
-  e.valid = validity_or_null(&a);
-  e.voff = a.offset;
-  e.boff = a.offset;
-  return e;
-}
-static int mx_check_out(const char* who, const pdx_mut_column* out, int want, int64_t n) {
-  if (!out) return fail(PDX_INVALID, std::string(who) + ": null output");
-  if (out->dtype != want) return fail(PDX_INVALID, std::string(who) + ": output dtype " + dtype_name(out->dtype) + ", the result is " + dtype_name(want));
-  if (out->length < n) return fail(PDX_INVALID, std::string(who) + ": output too small");
-  if (n > 0 && !out->values) return fail(PDX_INVALID, std::string(who) + ": null output buffer");
-  return PDX_OK;
-}
-// the table on the device, a zeroed null counter when the count has to come from the kernel
-static int mx_upload(Scratch& s, const std::vector<MxCol>& host, bool count, const MxCol** tab, unsigned long long** nulls, hipStream_t st) {
-  MxCol* t = s.get<MxCol>(host.size());
-  PDX_SCRATCH_CHECK(s);
-  if (!host.empty()) PDX_HIP(hipMemcpyAsync(t, host.data(), sizeof(MxCol) * host.size(), hipMemcpyHostToDevice, st));
-  *tab = t;
-  *nulls = nullptr;
-  if (count) {
-    *nulls = s.get<unsigned long long>(1);
-    PDX_SCRATCH_CHECK(s);
-    PDX_HIP(hipMemsetAsync(*nulls, 0, sizeof(unsigned long long), st));
-  }
-  return PDX_OK;
-}
-static int mx_read_nulls(const unsigned long long* nulls, pdx_mut_column* out, hipStream_t st) {
-  unsigned long long h = 0;
-  void* pin = pinned_slot();
-  PDX_HIP(hipMemcpyAsync(pin ? pin : &h, nulls, sizeof(h), hipMemcpyDeviceToHost, st));
-  PDX_HIP(hipStreamSynchronize(st));
-  if (pin) memcpy(&h, pin, sizeof(h));
-  out->null_count = (int64_t)h;
-  return PDX_OK;
-}
-static bool mx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <typename T>
-static void mx_launch_minmax(bool clip, const MxCol* tab, int nscalar, int C, int64_t n, int is_max, int skip, pdx_mut_column* out, unsigned long long* nulls,
+static void mx_launch_minmax(bool clip, const ColView* tab, int nscalar, int C, int64_t n, int is_max, int skip, pdx_mut_column* out, unsigned long long* nulls,
                              hipStream_t st) {
   const dim3 grid(grid_for(n, 256)), block(256);
   T* o = static_cast<T*>(out->values);
@@ -521,7 +420,7 @@ static int mx_minmax(const char* who, bool clip, int is_max, const std::vector<c
     for (size_t k = 1; k < (clip ? 2 : scalars.size() + arrays.size()); ++k) types += ", bool";
     return fail(PDX_NOT_IMPLEMENTED, std::string("Function '") + (is_max && !clip ? "max_element_wise" : "min_element_wise") + "' has no kernel matching input types (" + types + ")");
   }
-  PDX_TRY(mx_check_out(who, out, dt, n));
+  PDX_TRY(check_out(who, out, dt, n));
   // can a row be null?  skip_nulls: only when every operand can be; otherwise as soon as one can.  (A scalar with a bitmap and
   // null_count != 0 may be null: its bit is on the device.)
   bool any_v = false, all_v = true;
@@ -536,17 +435,18 @@ static int mx_minmax(const char* who, bool clip, int is_max, const std::vector<c
   out->length = n;
   out->null_count = 0;
   if (n == 0) return PDX_OK;
-  std::vector<MxCol> host;
+  std::vector<ColView> host;
   if (clip) {
-    host = {mx_entry(*arrays[0]), mx_entry(*scalars[0]), mx_entry(*scalars[1])};
+    host = {col_view(*arrays[0]), col_view(*scalars[0]), col_view(*scalars[1])};
   } else {
-    for (const pdx_column* c : scalars) host.push_back(mx_entry(*c));
-    for (const pdx_column* c : arrays) host.push_back(mx_entry(*c));
+    for (const pdx_column* c : scalars) host.push_back(col_view(*c));
+    for (const pdx_column* c : arrays) host.push_back(col_view(*c));
   }
   Scratch s;
-  const MxCol* tab;
-  unsigned long long* nulls;
-  PDX_TRY(mx_upload(s, host, may_null, &tab, &nulls, st));
+  const ColView* tab;
+  unsigned long long* nulls = nullptr;
+  PDX_TRY(upload_views(s, host, st, &tab));
+  if (may_null) PDX_TRY(open_null_counter(s, st, &nulls));
   const int ns = clip ? 0 : (int)scalars.size(), C = (int)host.size();
   switch (dt) {
     case PDX_FLOAT64: mx_launch_minmax<double>(clip, tab, ns, C, n, is_max, skip_nulls, out, nulls, st); break;
@@ -556,7 +456,7 @@ static int mx_minmax(const char* who, bool clip, int is_max, const std::vector<c
     default: mx_launch_minmax<int64_t>(clip, tab, ns, C, n, is_max, skip_nulls, out, nulls, st); break;
   }
   PDX_LAUNCH_CHECK();
-  if (may_null) return mx_read_nulls(nulls, out, st);
+  if (may_null) return read_back(&out->null_count, nulls, sizeof(out->null_count), st);
   return PDX_OK;
 }
 
@@ -564,7 +464,7 @@ template <typename Pred>
 static int mx_nonzero(const char* who, int64_t n, Pred pred, int64_t* out_count, pdx_mut_column* out, hipStream_t st) {
   Scratch s;
   if (out_count) return count_if(n, pred, out_count, s, st);
-  PDX_TRY(mx_check_out(who, out, PDX_UINT64, 0));
+  PDX_TRY(check_out(who, out, PDX_UINT64, 0));
   int64_t m = 0;
   const int64_t nblocks = ceil_div(n, kCompactTile);
   int64_t* counts = nullptr;
@@ -625,7 +525,7 @@ int pdx_coalesce(const pdx_column* cols, int ncols, pdx_mut_column* out, void* s
                                            " (cast to one type first)");
     if (cols[c].length != n) return fail(PDX_INVALID, std::string(who) + ": Array arguments must all be the same length");
   }
-  PDX_TRY(mx_check_out(who, out, dt, n));
+  PDX_TRY(check_out(who, out, dt, n));
   const bool may_null = validity_or_null(&cols[0]) != nullptr;
   if (may_null && !out->validity) return fail(PDX_INVALID, std::string(who) + ": the result can hold nulls but output has no validity buffer");
   hipStream_t st = as_stream(stream);
@@ -633,18 +533,19 @@ int pdx_coalesce(const pdx_column* cols, int ncols, pdx_mut_column* out, void* s
   out->null_count = 0;
   if (n == 0) return PDX_OK;
   // the columns behind the first one without a bitmap never give a value
-  std::vector<MxCol> host;
-  bool vec = is_narrow(dt) && mx_aligned16(out->values);
+  std::vector<ColView> host;
+  bool vec = is_narrow(dt) && aligned16(out->values);
   for (int c = 0; c < ncols; ++c) {
-    host.push_back(mx_entry(cols[c]));
-    vec = vec && mx_aligned16(host.back().values);
+    host.push_back(col_view(cols[c]));
+    vec = vec && aligned16(host.back().values);
     if (!host.back().valid) break;
   }
   const bool count = host.back().valid != nullptr;  // (a column without a bitmap leaves no row null)
   Scratch s;
-  const MxCol* tab;
-  unsigned long long* nulls;
-  PDX_TRY(mx_upload(s, host, count, &tab, &nulls, st));
+  const ColView* tab;
+  unsigned long long* nulls = nullptr;
+  PDX_TRY(upload_views(s, host, st, &tab));
+  if (count) PDX_TRY(open_null_counter(s, st, &nulls));
   const int C = (int)host.size();
   uint8_t* ov = static_cast<uint8_t*>(out->validity);
   if (dt == PDX_BOOL) {
@@ -656,7 +557,7 @@ int pdx_coalesce(const pdx_column* cols, int ncols, pdx_mut_column* out, void* s
     hipLaunchKernelGGL((k_coalesce<uint64_t, 1>), dim3(grid_for(n, 256)), dim3(256), 0, st, tab, C, n, static_cast<uint64_t*>(out->values), ov, nulls);
   }
   PDX_LAUNCH_CHECK();
-  if (count) return mx_read_nulls(nulls, out, st);
+  if (count) return read_back(&out->null_count, nulls, sizeof(out->null_count), st);
   return PDX_OK;
 }
 
@@ -694,15 +595,15 @@ int pdx_replace_with_mask(const pdx_column* a, const pdx_column* mask, const pdx
   PDX_TRY(check_column(repl, who, true));
   if (!mx_known_dtype(a->dtype)) return fail(PDX_INVALID, "pdx_replace_with_mask: unknown dtype");
   if (mask->dtype != PDX_BOOL)
-    return fail(PDX_INVALID, std::string("Function 'replace_with_mask' has no kernel matching input types (") + mx_arrow_name(a->dtype) + ", " + mx_arrow_name(mask->dtype) +
-                                 ", " + mx_arrow_name(repl->dtype) + ")");
+    return fail(PDX_INVALID, std::string("Function 'replace_with_mask' has no kernel matching input types (") + arrow_dtype_name(a->dtype) + ", " + arrow_dtype_name(mask->dtype) +
+                                 ", " + arrow_dtype_name(repl->dtype) + ")");
   if (repl->dtype != a->dtype)
-    return fail(PDX_INVALID, std::string("Function 'replace_with_mask' has no kernel matching input types (") + mx_arrow_name(a->dtype) + ", bool, " +
-                                 mx_arrow_name(repl->dtype) + ")");
+    return fail(PDX_INVALID, std::string("Function 'replace_with_mask' has no kernel matching input types (") + arrow_dtype_name(a->dtype) + ", bool, " +
+                                 arrow_dtype_name(repl->dtype) + ")");
   const int64_t n = a->length;
   if (mask->length != n)
     return fail(PDX_INVALID, "Mask must be of same length as array (expected " + std::to_string(n) + " items but got " + std::to_string(mask->length) + " items)");
-  PDX_TRY(mx_check_out(who, out, a->dtype, n));
+  PDX_TRY(check_out(who, out, a->dtype, n));
   const bool may_null = validity_or_null(a) || validity_or_null(mask) || validity_or_null(repl);
   if (may_null && !out->validity) return fail(PDX_INVALID, std::string(who) + ": the result can hold nulls but output has no validity buffer");
   hipStream_t st = as_stream(stream);
@@ -771,21 +672,20 @@ int pdx_all_valid_mask(const pdx_column* cols, int ncols, pdx_mut_column* out_ma
   if (!cols || ncols <= 0) return fail(PDX_INVALID, "pdx_all_valid_mask: at least one column is required");
   if (ncols > kMxMaxCols) return fail(PDX_INVALID, "pdx_all_valid_mask: more than " + std::to_string(kMxMaxCols) + " columns");
   const int64_t n = cols[0].length;
-  std::vector<MxCol> host;
+  std::vector<ColView> host;
   for (int c = 0; c < ncols; ++c) {
     PDX_TRY(check_column(&cols[c], who, true));
     if (cols[c].length != n) return fail(PDX_INVALID, std::string(who) + ": all columns must have the same length");
-    if (validity_or_null(&cols[c])) host.push_back(mx_entry(cols[c]));
+    if (validity_or_null(&cols[c])) host.push_back(col_view(cols[c]));
   }
-  PDX_TRY(mx_check_out(who, out_mask, PDX_BOOL, n));
+  PDX_TRY(check_out(who, out_mask, PDX_BOOL, n));
   hipStream_t st = as_stream(stream);
   out_mask->length = n;
   out_mask->null_count = 0;
   if (n == 0) return PDX_OK;
   Scratch s;
-  const MxCol* tab;
-  unsigned long long* nulls;
-  PDX_TRY(mx_upload(s, host, false, &tab, &nulls, st));
+  const ColView* tab;
+  PDX_TRY(upload_views(s, host, st, &tab));
   hipLaunchKernelGGL(k_all_valid, dim3(grid_for((n + 63) >> 6, 256)), dim3(256), 0, st, tab, (int)host.size(), n, static_cast<uint8_t*>(out_mask->values));
   PDX_LAUNCH_CHECK();
   return PDX_OK;

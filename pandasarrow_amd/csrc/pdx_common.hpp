@@ -138,7 +138,8 @@ inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 // Arrow bitmap: bit i lives in byte i>>3, position i&7 (LSB first).
 __device__ __forceinline__ bool bit_get(const uint8_t* bits, int64_t i) { return (bits[i >> 3] >> (i & 7)) & 1; }
 // 64 consecutive bits starting at bit position `bitpos` (may be unaligned).  Reads up to 9 bytes; callers guarantee
-// that reading bytes up to (bitpos+63)>>3 is in bounds or pass `limit_bits` to clamp.
+// that reading bytes up to (bitpos+63)>>3 is in bounds or pass `limit_bits` to clamp.  The per-lane, byte-granular form; a window whose
+// operands are wave-uniform is colview.hpp's load_bits64_uniform.
 __device__ __forceinline__ uint64_t load_bits64(const uint8_t* bits, int64_t bitpos, int64_t limit_bits) {
   // limit_bits: total number of addressable bits from bit 0 of `bits` (exclusive end); bits past it read as 0
   int64_t byte0 = bitpos >> 3;
@@ -181,6 +182,7 @@ int check_column(const pdx_column* c, const char* what, bool narrow_ok = false);
 inline bool is_narrow(int dt) { return dt == PDX_INT32 || dt == PDX_FLOAT32; }
 inline int dtype_bytes(int dt) { return is_narrow(dt) ? 4 : 8; }
 const char* dtype_name(int dt);
+const char* arrow_dtype_name(int dt);  // Arrow's spelling, for "has no kernel matching input types (...)": double / float, else as dtype_name
 inline bool is_int_like(int dt) { return dt == PDX_INT64 || dt == PDX_UINT64 || dt == PDX_TIMESTAMP_NS; }
 inline const uint8_t* validity_or_null(const pdx_column* c) {
   return (c->validity && c->null_count != 0) ? static_cast<const uint8_t*>(c->validity) : nullptr;

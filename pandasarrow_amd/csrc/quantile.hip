@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <map>
 #include <vector>
+#include "colview.hpp"
 #include "group_order.hpp"
 #include "quantile.hpp"
 #include "radix_sort.hpp"
@@ -358,12 +359,6 @@ struct QHostSeg {
   bool in_newest;
 };
 
-static int q_copy_sync(void* dst, const void* src, size_t bytes, hipStream_t st) {
-  PDX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-  PDX_HIP(hipStreamSynchronize(st));
-  return PDX_OK;
-}
-
 // Level 0 over the column, then whatever levels the ranks need.  make_ranks(n, valid_rows) is called once n is known (after the first
 // histogram) and returns the distinct ranks wanted (an empty list ends the run); out: key, place among equal keys, sign of a zero.
 template <typename T, typename MakeRanks>
@@ -419,7 +414,7 @@ static int q_select(const pdx_column* a, MakeRanks make_ranks, std::vector<QTarg
     hipLaunchKernelGGL(k_q_fold, dim3(kQBins / kQBlock, (unsigned)((total_blocks + kQFoldSlice - 1) / kQFoldSlice)), dim3(kQBlock), 0, st, dsegs, nseg, partial,
                        (uint32_t)total_blocks, hist);
     PDX_LAUNCH_CHECK();
-    PDX_TRY(q_copy_sync(hh.data(), hist, sizeof(unsigned long long) * hh.size(), st));
+    PDX_TRY(read_back(hh.data(), hist, sizeof(unsigned long long) * hh.size(), st));
     const unsigned long long* hmm = hh.data() + (size_t)nseg * kQBins;  // [2 sg], [2 sg + 1]: smallest / largest key of segment sg
     const size_t valid_total_index = (size_t)nseg * kQBins + 2 * (size_t)nseg;
     if (level0) {
@@ -543,7 +538,7 @@ static int q_select(const pdx_column* a, MakeRanks make_ranks, std::vector<QTarg
     PDX_HIP(hipMemcpyAsync(dp, picks.data(), sizeof(QPick) * picks.size(), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_q_small<K>, dim3((unsigned)picks.size()), dim3(kQBlock), 0, st, dp, dr);
     PDX_LAUNCH_CHECK();
-    PDX_TRY(q_copy_sync(hr.data(), dr, sizeof(QPicked) * picks.size(), st));
+    PDX_TRY(read_back(hr.data(), dr, sizeof(QPicked) * picks.size(), st));
     for (size_t j = 0; j < picks.size(); ++j) {
       QTarget<K>& x = tg[(size_t)pick_target[j]];
       x.done = true;
@@ -565,7 +560,7 @@ static int q_select(const pdx_column* a, MakeRanks make_ranks, std::vector<QTarg
       hipLaunchKernelGGL(k_q_zero_count<T>, dim3(nb), dim3(kQBlock), 0, st, values, valid, voff, n, chunk, counts);
       PDX_LAUNCH_CHECK();
       std::vector<unsigned long long> hc(nb);
-      PDX_TRY(q_copy_sync(hc.data(), counts, sizeof(unsigned long long) * nb, st));
+      PDX_TRY(read_back(hc.data(), counts, sizeof(unsigned long long) * nb, st));
       std::vector<QZeroPick> zp;  // every zero target: one launch, one copy back
       std::vector<size_t> zp_target;
       for (size_t t = 0; t < tg.size(); ++t) {
@@ -585,7 +580,7 @@ static int q_select(const pdx_column* a, MakeRanks make_ranks, std::vector<QTarg
       PDX_HIP(hipMemcpyAsync(dzp, zp.data(), sizeof(QZeroPick) * zp.size(), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_q_zero_pick<T>, dim3((unsigned)zp.size()), dim3(kQBlock), 0, st, values, valid, voff, dzp, neg);
       PDX_LAUNCH_CHECK();
-      PDX_TRY(q_copy_sync(hn.data(), neg, sizeof(uint32_t) * zp.size(), st));
+      PDX_TRY(read_back(hn.data(), neg, sizeof(uint32_t) * zp.size(), st));
       for (size_t k = 0; k < zp.size(); ++k) tg[zp_target[k]].negative_zero = hn[k] != 0;
     }
   }
@@ -811,7 +806,7 @@ static int groupby_quantile_typed(pdx_groupby* gb, const pdx_column* values, con
                        nulls + k);
   PDX_LAUNCH_CHECK();
   std::vector<unsigned long long> hn((size_t)nq);
-  PDX_TRY(q_copy_sync(hn.data(), nulls, sizeof(unsigned long long) * (size_t)nq, st));
+  PDX_TRY(read_back(hn.data(), nulls, sizeof(unsigned long long) * (size_t)nq, st));
   for (int k = 0; k < nq; ++k) {
     outs[k].length = G;
     outs[k].null_count = (int64_t)hn[k];

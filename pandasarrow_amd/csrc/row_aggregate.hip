@@ -3,9 +3,9 @@
 //
 // Shape: a lane owns a row, a wave owns 64 consecutive rows.  A column read is one contiguous 512-byte (256 for 4-byte values) access
 // per wave; the column loop runs inside the lane, kRowU column loads issued before the first is consumed.  The columns come as a device
-// table (RowCol) that every wave reads with uniform loads, as it reads one 64-bit validity word per column.  Output validity is one
+// table (ColView) that every wave reads with uniform loads, as it reads one 64-bit validity word per column.  Output validity is one
 // ballot per wave.  Every input byte is read once (twice for variance / stddev, whose second pass re-reads the row); no scratch but
-// the table and the null counter.
+// the table and the null counter.  The table, the bitmap windows and stores and the null counting are colview.hpp's.
 //
 // Bit parity with Arrow C++ 25: the fp64 sum of a row is pairwise.hpp's tree in column order (16-value leaves restarting at every run
 // of valid cells, binary-counter merge, the NaN rule of each site), held per lane in registers (RowTree); variance is the two passes
@@ -15,19 +15,14 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include "colview.hpp"
 #include "pairwise.hpp"
 
 namespace pdx {
 
 constexpr int kRowU = 8;             // column loads in flight per lane
-constexpr int kRowMaxCols = 2046;    // RowTree<10> holds the 1023 leaves of 2046 alternating cells
+constexpr int kRowMaxCols = 2046;    // RowTree<10> holds the 1023 leaves of 2046 alternating cells (multiplex.hip's kMxMaxCols follows it)
 
-struct RowCol {
-  const void* values;    // element offset applied (PDX_BOOL: the bitmap's base)
-  const uint8_t* valid;  // nullptr: every row is valid
-  int64_t voff;          // bit offset into valid
-  int64_t boff;          // PDX_BOOL: bit offset into values
-};
 struct RowOpts {
   int kind, skip, min_count, ddof;  // min_count clamped to [0, C + 1] by the host
 };
@@ -37,31 +32,6 @@ struct RowOut {
   unsigned long long* nulls;   // nullptr: the host knows the count
 };
 
-// 64 bits starting at bit `bitpos` of `bits`, of which the caller uses the first `nbits`: two aligned 64-bit words and a funnel shift.
-// Every word read holds at least one byte of the `nbits` asked for, so no read leaves the pages of the bitmap.  All operands are
-// wave-uniform: the loads are scalar.
-__device__ __forceinline__ uint64_t row_bits64(const uint8_t* bits, int64_t bitpos, int nbits) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(bits) + (uintptr_t)(bitpos >> 3);
-  // (the inputs are never written while the kernel runs: the constant address space is what lets a uniform address become a scalar load)
-  const __attribute__((address_space(4))) uint64_t* p = (const __attribute__((address_space(4))) uint64_t*)(a & ~(uintptr_t)7);
-  const int sh = (int)(a & 7) * 8 + (int)(bitpos & 7);
-  uint64_t r = p[0] >> sh;
-  if (sh + nbits > 64) r |= p[1] << (64 - sh);
-  return r;
-}
-// eight rows of a bit-packed output per lane 0..7; the byte that holds row n keeps its bits from n on
-__device__ __forceinline__ void row_store_bits(uint8_t* dst, int64_t w, int64_t n, uint64_t word, int lane) {
-  if (lane >= 8) return;
-  const int64_t r0 = (w << 6) + lane * 8;
-  if (r0 >= n) return;
-  uint8_t b = (uint8_t)(word >> (8 * lane));
-  const int64_t rem = n - r0;
-  if (rem < 8) {
-    const uint8_t m = (uint8_t)((1u << rem) - 1u);
-    b = (uint8_t)((dst[(w << 3) + lane] & ~m) | (b & m));
-  }
-  dst[(w << 3) + lane] = b;
-}
 // the null rule every kind but count shares: ScalarAggregateOptions{skip_nulls, min_count} against nv valid cells of C
 __device__ __forceinline__ bool row_has_result(const RowOpts& p, int nv, int C) { return (p.skip || nv == C) && nv >= p.min_count; }
 
@@ -305,29 +275,21 @@ struct RowVar {
   }
 };
 
-// the wave's first row word and the number of waves in the grid, as values the compiler knows to be wave-uniform
-__device__ __forceinline__ int row_first_word() { return __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)); }
-
 template <typename R>
 __device__ __forceinline__ void row_emit(const RowOut& o, int64_t w, int64_t n, int lane, bool in, bool ok, R r, unsigned long long& nc) {
   if (in) static_cast<R*>(o.values)[(w << 6) + lane] = ok ? r : R(0);
   if (o.valid) {
-    row_store_bits(o.valid, w, n, __ballot(ok), lane);
+    store_bits_wave(o.valid, w, n, __ballot(ok), lane);
     if (in && !ok) ++nc;
   }
 }
-__device__ __forceinline__ void row_count_nulls(const RowOut& o, int lane, unsigned long long nc) {
-  if (!o.nulls) return;
-  for (int d = 32; d > 0; d >>= 1) nc += __shfl_down(nc, d, 64);
-  if (lane == 0 && nc) atomicAdd(o.nulls, nc);
-}
 
 template <typename T, typename Op>
-__global__ void __launch_bounds__(256) k_row_agg(const RowCol* __restrict__ tab, int ncols, int64_t n, RowOpts p, RowOut o) {
+__global__ void __launch_bounds__(256) k_row_agg(const ColView* __restrict__ tab, int ncols, int64_t n, RowOpts p, RowOut o) {
   const int lane = threadIdx.x & 63;
   const int64_t nwords = (n + 63) >> 6, nwaves = (int64_t)(gridDim.x * blockDim.x) >> 6;
   unsigned long long nc = 0;
-  for (int64_t w = row_first_word(); w < nwords; w += nwaves) {
+  for (int64_t w = first_word_of_wave(); w < nwords; w += nwaves) {
     const int64_t base = w << 6, i = base + lane;
     const bool in = i < n;
     const int nbits = n - base < 64 ? (int)(n - base) : 64;
@@ -343,8 +305,8 @@ __global__ void __launch_bounds__(256) k_row_agg(const RowCol* __restrict__ tab,
           v[u] = T(0);
           vw[u] = 0;
           if (c0 + u < ncols) {
-            const RowCol e = tab[c0 + u];
-            vw[u] = e.valid ? row_bits64(e.valid, e.voff + base, nbits) : ~0ull;
+            const ColView e = tab[c0 + u];
+            vw[u] = e.valid ? load_bits64_uniform(e.valid, e.voff + base, nbits) : ~0ull;
             if (in) v[u] = ((const __attribute__((address_space(1))) T*)e.values)[i];  // (a global load, not a flat one: the table hides the address space)
           }
         }
@@ -357,45 +319,45 @@ __global__ void __launch_bounds__(256) k_row_agg(const RowCol* __restrict__ tab,
     const bool ok = op.finish(p, ncols, r) && in;
     row_emit(o, w, n, lane, in, ok, r, nc);
   }
-  row_count_nulls(o, lane, nc);
+  if (o.nulls) wave_add_nulls(o.nulls, lane, nc);
 }
 
 // count / count_null: the validity words alone -> int64, never null
-__global__ void __launch_bounds__(256) k_row_count(const RowCol* __restrict__ tab, int ncols, int64_t n, int only_null, long long* __restrict__ out,
+__global__ void __launch_bounds__(256) k_row_count(const ColView* __restrict__ tab, int ncols, int64_t n, int only_null, long long* __restrict__ out,
                                                    uint8_t* __restrict__ ovalid) {
   const int lane = threadIdx.x & 63;
   const int64_t nwords = (n + 63) >> 6, nwaves = (int64_t)(gridDim.x * blockDim.x) >> 6;
-  for (int64_t w = row_first_word(); w < nwords; w += nwaves) {
+  for (int64_t w = first_word_of_wave(); w < nwords; w += nwaves) {
     const int64_t base = w << 6, i = base + lane;
     const int nbits = n - base < 64 ? (int)(n - base) : 64;
     int nv = 0;
     for (int c = 0; c < ncols; ++c) {
-      const RowCol e = tab[c];
-      const uint64_t vw = e.valid ? row_bits64(e.valid, e.voff + base, nbits) : ~0ull;
+      const ColView e = tab[c];
+      const uint64_t vw = e.valid ? load_bits64_uniform(e.valid, e.voff + base, nbits) : ~0ull;
       nv += (int)((vw >> lane) & 1ull);
     }
     if (i < n) out[i] = only_null ? ncols - nv : nv;
-    if (ovalid) row_store_bits(ovalid, w, n, ~0ull, lane);
+    if (ovalid) store_bits_wave(ovalid, w, n, ~0ull, lane);
   }
 }
 
 // all / any of bit-packed cells: a value word and a validity word per column and wave.  skip_nulls: over the valid cells (none: all is
 // true, any false); otherwise a null cell makes the row null unless a valid cell already decides it (a false for all, a true for any).
-__global__ void __launch_bounds__(256) k_row_all_any(const RowCol* __restrict__ tab, int ncols, int64_t n, RowOpts p, RowOut o) {
+__global__ void __launch_bounds__(256) k_row_all_any(const ColView* __restrict__ tab, int ncols, int64_t n, RowOpts p, RowOut o) {
   const int lane = threadIdx.x & 63;
   const int64_t nwords = (n + 63) >> 6, nwaves = (int64_t)(gridDim.x * blockDim.x) >> 6;
   const bool is_all = p.kind == PDX_AGG_ALL;
   unsigned long long nc = 0;
-  for (int64_t w = row_first_word(); w < nwords; w += nwaves) {
+  for (int64_t w = first_word_of_wave(); w < nwords; w += nwaves) {
     const int64_t base = w << 6;
     const bool in = base + lane < n;
     const int nbits = n - base < 64 ? (int)(n - base) : 64;
     uint64_t seen_true = 0, seen_false = 0, full = ~0ull;  // per row: a valid true cell, a valid false cell, no null cell
     int nv = 0;
     for (int c = 0; c < ncols; ++c) {
-      const RowCol e = tab[c];
-      const uint64_t vw = e.valid ? row_bits64(e.valid, e.voff + base, nbits) : ~0ull;
-      const uint64_t bw = row_bits64(static_cast<const uint8_t*>(e.values), e.boff + base, nbits);
+      const ColView e = tab[c];
+      const uint64_t vw = e.valid ? load_bits64_uniform(e.valid, e.voff + base, nbits) : ~0ull;
+      const uint64_t bw = load_bits64_uniform(static_cast<const uint8_t*>(e.values), e.boff + base, nbits);
       seen_true |= vw & bw;
       seen_false |= vw & ~bw;
       full &= vw;
@@ -404,13 +366,13 @@ __global__ void __launch_bounds__(256) k_row_all_any(const RowCol* __restrict__ 
     const uint64_t value = is_all ? ~seen_false : seen_true;
     const uint64_t decided = is_all ? seen_false : seen_true;
     const bool ok = in && nv >= p.min_count && (p.skip || (((full | decided) >> lane) & 1ull));
-    row_store_bits(static_cast<uint8_t*>(o.values), w, n, value & __ballot(ok), lane);
+    store_bits_wave(static_cast<uint8_t*>(o.values), w, n, value & __ballot(ok), lane);
     if (o.valid) {
-      row_store_bits(o.valid, w, n, __ballot(ok), lane);
+      store_bits_wave(o.valid, w, n, __ballot(ok), lane);
       if (in && !ok) ++nc;
     }
   }
-  row_count_nulls(o, lane, nc);
+  if (o.nulls) wave_add_nulls(o.nulls, lane, nc);
 }
 
 // ---------------------------------------------------------------- host side
@@ -418,16 +380,9 @@ static const char* row_kind_name(int kind) {
   static const char* const kNames[] = {"sum", "mean", "min", "max", "count", "variance", "stddev", "product", "first", "last", "all", "any", "count_distinct", "count"};
   return kNames[kind];
 }
-static const char* arrow_type_name(int dt) {
-  switch (dt) {
-    case PDX_FLOAT64: return "double";
-    case PDX_FLOAT32: return "float";
-    default: return dtype_name(dt);
-  }
-}
 
 template <typename T, typename Op>
-static void row_launch(const RowCol* tab, int C, int64_t n, const RowOpts& p, const RowOut& o, hipStream_t st) {
+static void row_launch(const ColView* tab, int C, int64_t n, const RowOpts& p, const RowOut& o, hipStream_t st) {
   // rows per thread 1: a lane's state is a row; the grid strides over 64-row words
   hipLaunchKernelGGL((k_row_agg<T, Op>), dim3(grid_for(n, 256)), dim3(256), 0, st, tab, C, n, p, o);
 }
@@ -438,7 +393,7 @@ static int row_tree_levels(int C, bool any_validity) {
   return leaves < 16 ? 4 : leaves < 128 ? 7 : 10;
 }
 template <typename T, template <typename, int> class Op>
-static void row_launch_tree(int levels, const RowCol* tab, int C, int64_t n, const RowOpts& p, const RowOut& o, hipStream_t st) {
+static void row_launch_tree(int levels, const ColView* tab, int C, int64_t n, const RowOpts& p, const RowOut& o, hipStream_t st) {
   switch (levels) {
     case 0: return row_launch<T, Op<T, 0>>(tab, C, n, p, o, st);
     case 4: return row_launch<T, Op<T, 4>>(tab, C, n, p, o, st);
@@ -484,7 +439,7 @@ extern "C" int pdx_row_aggregate(int kind, const pdx_column* cols, int ncols, in
     default: return fail(PDX_INVALID, std::string(who) + ": unknown dtype");
   }
   if (!accepted)
-    return fail(PDX_NOT_IMPLEMENTED, std::string("Function '") + row_kind_name(kind) + "' has no kernel matching input types (" + arrow_type_name(dt) + ")");
+    return fail(PDX_NOT_IMPLEMENTED, std::string("Function '") + row_kind_name(kind) + "' has no kernel matching input types (" + arrow_dtype_name(dt) + ")");
   const bool is_f = dt == PDX_FLOAT64 || dt == PDX_FLOAT32;
   int want;
   if (is_count) want = PDX_INT64;
@@ -492,10 +447,7 @@ extern "C" int pdx_row_aggregate(int kind, const pdx_column* cols, int ncols, in
   else if (keeps_dtype) want = dt;
   else if (kind == PDX_AGG_SUM || kind == PDX_AGG_PRODUCT) want = is_f ? PDX_FLOAT64 : dt == PDX_UINT64 ? PDX_UINT64 : PDX_INT64;
   else want = PDX_FLOAT64;
-  if (!out) return fail(PDX_INVALID, std::string(who) + ": null output");
-  if (out->dtype != want) return fail(PDX_INVALID, std::string(who) + ": output dtype " + dtype_name(out->dtype) + ", the result is " + dtype_name(want));
-  if (out->length < n) return fail(PDX_INVALID, std::string(who) + ": output too small");
-  if (n > 0 && !out->values) return fail(PDX_INVALID, std::string(who) + ": null output buffer");
+  PDX_TRY(check_out(who, out, want, n));
   RowOpts p;
   p.kind = kind;
   p.skip = skip_nulls != 0;
@@ -514,28 +466,16 @@ extern "C" int pdx_row_aggregate(int kind, const pdx_column* cols, int ncols, in
   if (n == 0) return PDX_OK;
 
   Scratch s;
-  RowCol* tab = s.get<RowCol>((size_t)C);
-  PDX_SCRATCH_CHECK(s);
-  std::vector<RowCol> host((size_t)C);
-  for (int c = 0; c < C; ++c) {
-    const pdx_column& a = cols[c];
-    RowCol& e = host[(size_t)c];
-    e.values = dt == PDX_BOOL ? a.values : static_cast<const void*>(static_cast<const char*>(a.values) + (size_t)a.offset * (size_t)dtype_bytes(dt));
-    e.valid = validity_or_null(&a);
-    e.voff = a.offset;
-    e.boff = a.offset;
-  }
-  PDX_HIP(hipMemcpyAsync(tab, host.data(), sizeof(RowCol) * (size_t)C, hipMemcpyHostToDevice, st));
+  std::vector<ColView> host;
+  for (int c = 0; c < C; ++c) host.push_back(col_view(cols[c]));
+  const ColView* tab;
+  PDX_TRY(upload_views(s, host, st, &tab));
   RowOut o;
   o.values = out->values;
   o.valid = static_cast<uint8_t*>(out->validity);
   o.nulls = nullptr;
   const bool count_on_device = may_null && any_validity && !all_valid_null;
-  if (count_on_device) {
-    o.nulls = s.get<unsigned long long>(1);
-    PDX_SCRATCH_CHECK(s);
-    PDX_HIP(hipMemsetAsync(o.nulls, 0, sizeof(unsigned long long), st));
-  }
+  if (count_on_device) PDX_TRY(open_null_counter(s, st, &o.nulls));
   const dim3 grid(grid_for(n, 256)), block(256);
   if (is_count) {
     hipLaunchKernelGGL(k_row_count, grid, block, 0, st, tab, C, n, (int)(kind == PDX_AGG_COUNT_NULL), static_cast<long long*>(out->values),
@@ -579,13 +519,6 @@ extern "C" int pdx_row_aggregate(int kind, const pdx_column* cols, int ncols, in
   PDX_LAUNCH_CHECK();
   // the null count is known on the host unless rows differ, i.e. a column brings a bitmap: only then is it read back (the one host wait)
   if (all_valid_null) out->null_count = n;
-  else if (count_on_device) {
-    unsigned long long h = 0;
-    void* pin = pinned_slot();
-    PDX_HIP(hipMemcpyAsync(pin ? pin : &h, o.nulls, sizeof(h), hipMemcpyDeviceToHost, st));
-    PDX_HIP(hipStreamSynchronize(st));
-    if (pin) memcpy(&h, pin, sizeof(h));
-    out->null_count = (int64_t)h;
-  }
+  else if (count_on_device) PDX_TRY(read_back(&out->null_count, o.nulls, sizeof(out->null_count), st));
   return PDX_OK;
 }

@@ -35,6 +35,13 @@ const char* dtype_name(int dt) {
     default: return "unknown";
   }
 }
+const char* arrow_dtype_name(int dt) {
+  switch (dt) {
+    case PDX_FLOAT64: return "double";
+    case PDX_FLOAT32: return "float";
+    default: return dtype_name(dt);
+  }
+}
 
 int check_column(const pdx_column* c, const char* what, bool narrow_ok) {
   if (!c) return fail(PDX_INVALID, std::string(what) + ": null column");

@@ -11,6 +11,7 @@
 // line is fetched once).  take is the same gather with caller indices plus a bounds check that reports through a device
 // flag.  Output validity words are assembled with wave ballots: a wave owns 64 consecutive output rows.
 // Algorithmic bytes: filter (1/8 + 8(C+1)(1+s)) B/row, take (8 + 16(C+1)) B per output row.
+#include "colview.hpp"
 #include "compact.hpp"
 
 namespace pdx {
@@ -376,8 +377,7 @@ __global__ void k_concat_validity(ConcatParts p, int64_t total, uint8_t* __restr
       for (int k = 0; k < nbytes; ++k) out[(w << 3) + k] = (uint8_t)(r >> (8 * k));
     }
   }
-  for (int d = 32; d > 0; d >>= 1) nc += __shfl_down(nc, d, 64);
-  if ((threadIdx.x & 63) == 0 && nc) atomicAdd(nulls, nc);
+  wave_add_nulls(nulls, threadIdx.x & 63, nc);
 }
 
 }  // namespace pdx

@@ -57,7 +57,8 @@ typedef enum pdx_dtype {
   PDX_UINT64 = 3,
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
-   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_mode, pdx_sort_indices, pdx_row_aggregate
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_mode, pdx_sort_indices, pdx_row_aggregate,
+   * the lookups (pdx_is_in ... pdx_dictionary_encode)
    * and the selection / multiplexing calls (pdx_coalesce ... pdx_all_valid_mask); every other entry point returns
    * PDX_NOT_IMPLEMENTED naming the dtype (the group-by does not take 4-byte keys yet, so value_counts of such a column is refused too).  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
    * widened (exactly) in v.f64. */
@@ -522,6 +523,45 @@ int pdx_mode(const pdx_column* a, int64_t n, int skip_nulls, int64_t min_count, 
 int pdx_mode_last_plan(char* buf, size_t buf_len);
 int pdx_groupby_mode(pdx_groupby* gb, const pdx_column* values, pdx_mut_column* out_modes, pdx_mut_column* out_counts, void* stream);
 int pdx_groupby_sizes(pdx_groupby* gb, int64_t* out_sizes /* G int64, device */, void* stream);
+
+/* ---------------------------------------------------------------- lookups: is_in / index_in, index, argmin / argmax, dictionary_encode
+ * Replace CallFunction("is_in" | "index_in", {array}, SetLookupOptions{value_set, skip_nulls}) (Series::is_in / index_in, src/series.cpp:632-640),
+ * CallFunction("index", {array}, IndexOptions{value}) and the index(min()) / index(max()) built on it (NDFrame::index / argmin / argmax,
+ * src/ndframe.h:276-282; Series::idxMin / idxMax, src/series.cpp:164-172; DataFrame::idxMin / idxMax, src/dataframe.cpp:496-512) and
+ * DictionaryEncode (Series::dictionary_encode, src/series.cpp:341).  Semantics = Arrow C++ 25.0.0, bit for bit (tests/golden/lookup_golden.npz).
+ * Common to all: a: PDX_INT64, PDX_UINT64, PDX_TIMESTAMP_NS, PDX_FLOAT64, PDX_INT32, PDX_FLOAT32; PDX_BOOL returns PDX_NOT_IMPLEMENTED naming the
+ * dtype.  Any offset, validity at any bit offset, null_count -1, a column without validity is all valid, int64 lengths; an empty input gives
+ * PDX_OK and length 0; rows, bytes and bits of an output beyond the result length are untouched; value bytes under a null row are zero;
+ * deterministic.  Every refusal happens before anything is launched.
+ *
+ * pdx_is_in / pdx_index_in: values match by BIT PATTERN (Arrow's memo table): 0.0 and -0.0 differ, NaNs of another sign or payload differ.
+ *   value_set: the dtype of `a` (PDX_INVALID otherwise: Arrow would cast the set, the facades do where pdx_cast is exact), at most 2^31-1
+ *   entries, duplicates and nulls allowed.  pdx_is_in: out PDX_BOOL, never null (validity not touched, null_count 0).  pdx_index_in: out
+ *   PDX_INT32 = the position of the value's FIRST occurrence in value_set, null where there is none (out->validity is required for a non-empty
+ *   input; null_count exact: it is read back, the call's only host wait -- pdx_is_in is asynchronous).  A null row: with skip_nulls == 0 it
+ *   matches the set's first null (true / its position) when the set holds one; otherwise false / null.  An empty set gives all false / null.
+ *   The set is deduplicated into an open-addressing table at load factor <= 0.5; sets of up to 2048 entries are probed from a copy in every
+ *   workgroup's LDS (PDX_LOOKUP_LDS_MAX=<entries> lowers that bound), larger ones where they were built.  pdx_lookup_last_plan (diagnostic,
+ *   this thread's last pdx_is_in / pdx_index_in; tests assert it): "plan=lds|global|empty set_size=<entries> slots=<table slots>".
+ * pdx_index: *out_row (host) = the first valid row with a[row] == value under IEEE == (0.0 finds -0.0), -1 when there is none; a null or NaN
+ *   value (value == NULL included) gives -1 and is not an error.  value->dtype must equal a's (PDX_INVALID), 4-byte values as pdx_scalar
+ *   documents; a value that a 4-byte column cannot hold (an integer outside int32, a double that is no float32) gives -1.  One pass that
+ *   stops behind the first match; synchronises `stream`.
+ * pdx_arg_extreme: out_rows[c] (host, ncols) = index(min(cols[c])) (is_max == 0) / index(max(cols[c])) in ONE read of every column: the row of
+ *   the smallest / largest valid value, the first such row on ties (0.0 == -0.0 tie); NaN never wins over a number; -1 when the column is
+ *   empty, all null, or its valid values are all NaN (Arrow's min is NaN then, which index never finds).  1 .. 65535 columns, which may
+ *   differ in dtype and length; one launch for all of them plus a small final kernel; synchronises `stream`.
+ * pdx_dictionary_encode: out_dict (a's dtype, capacity >= a->length, no nulls; its length is set on return) = the distinct bit patterns of
+ *   the valid rows in first-occurrence order; out_codes (PDX_INT32, >= a->length rows) = each row's position in it, null for a null row
+ *   (null_encoding = mask: a null takes no dictionary slot; out_codes->validity is required when `a` can hold a null).  Built on the
+ *   group-by handle over the 8-byte bit image (a 4-byte column is zero-extended first), whose limit it inherits: at most 2^31-1 rows
+ *   (PDX_NOT_IMPLEMENTED beyond).  Synchronises `stream`. */
+int pdx_is_in(const pdx_column* a, const pdx_column* value_set, int skip_nulls, pdx_mut_column* out, void* stream);
+int pdx_index_in(const pdx_column* a, const pdx_column* value_set, int skip_nulls, pdx_mut_column* out, void* stream);
+int pdx_lookup_last_plan(char* buf, size_t buf_len);
+int pdx_index(const pdx_column* a, const pdx_scalar* value /* NULL: the null scalar */, int64_t* out_row /* host */, void* stream);
+int pdx_arg_extreme(int is_max, const pdx_column* cols, int ncols, int64_t* out_rows /* host, ncols */, void* stream);
+int pdx_dictionary_encode(const pdx_column* a, pdx_mut_column* out_codes, pdx_mut_column* out_dict, void* stream);
 
 /* ---------------------------------------------------------------- exact multi-GPU fp64 sum (partial-tree exchange)
  * The reference's per-group sum is Arrow's pairwise tree over the group's rows in GLOBAL row order; with row-range shards a

@@ -142,6 +142,12 @@ ABI_SYMBOLS = {
     "pdx_mode_last_plan": (C.c_int, [C.c_char_p, C.c_size_t]),
     "pdx_groupby_mode": (C.c_int, [_P, _COL, _MUT, _MUT, _P]),
     "pdx_groupby_sizes": (C.c_int, [_P, _P, _P]),
+    "pdx_is_in": (C.c_int, [_COL, _COL, C.c_int, _MUT, _P]),
+    "pdx_index_in": (C.c_int, [_COL, _COL, C.c_int, _MUT, _P]),
+    "pdx_lookup_last_plan": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "pdx_index": (C.c_int, [_COL, C.POINTER(PdxScalar), C.POINTER(C.c_int64), _P]),
+    "pdx_arg_extreme": (C.c_int, [C.c_int, _COL, C.c_int, C.POINTER(C.c_int64), _P]),
+    "pdx_dictionary_encode": (C.c_int, [_COL, _MUT, _MUT, _P]),
     "pdx_groupby_group_values": (C.c_int, [_P, _COL, _P, C.POINTER(_P)]),
     "pdx_grouped_destroy": (C.c_int, [_P]),
     "pdx_grouped_counts": (C.c_int, [_P, _P, _P]),

@@ -88,6 +88,20 @@ def _take_filled(cols, idx, fill_value):
     return filled
 
 
+def _unique_narrow(col):
+    """unique() of a 4-byte column: pdx_dictionary_encode's dictionary, with the null (if any) put back where it first occurs -- behind
+    the values first seen before the first null row, i.e. after the largest code in front of it"""
+    codes, dic = K.dictionary_encode(col)
+    if codes.null_count == 0:
+        return dic
+    null_rows = K.indices_nonzero(K.invert(Column(L.BOOL, col.length, col.validity, None, col.offset)))
+    first_null = int(null_rows.slice(0, 1).to_numpy()[0][0])
+    before = K.aggregate(L.AGG_MAX, codes.slice(0, first_null))[0] if first_null else None
+    p = 0 if before is None else int(before) + 1
+    parts = [dic.slice(0, p), K.null_column(col.dtype, 1), dic.slice(p, dic.length - p)]
+    return K.concat([q for q in parts if q.length])
+
+
 class Scalar:
     """pd::Scalar (src/scalar.h:62-241): a value or null."""
 
@@ -363,8 +377,14 @@ class Series:
         return self._bool_counts("any")[0] > 0
 
     def unique(self):
-        """Series::unique: the distinct values in first-occurrence order (a null, if any, keeps its place) -- the group-by dictionary."""
+        """Series::unique: the distinct values in first-occurrence order (a null, if any, keeps its place) -- the group-by dictionary.
+        Distinct means distinct bit patterns (0.0 and -0.0, NaNs of different payload).  bool and the 4-byte dtypes go through
+        pdx_dictionary_encode / the 0 / 1 key of value_counts; the integer path is the group-by's own dictionary."""
         key = self.col
+        if key.dtype == L.BOOL:
+            return Series(K.value_counts(key)[0], name=self.name)
+        if key.dtype in (L.INT32, L.FLOAT32):
+            return Series(_unique_narrow(key), name=self.name)
         h = K.GroupByHandle.create(key if key.dtype != L.FLOAT64 else Column(L.INT64, key.length, key.values, key.validity, key.offset, key.null_count))
         u = h.unique_keys()
         if key.dtype == L.FLOAT64:
@@ -375,6 +395,58 @@ class Series:
         """Series::nunique: distinct VALID values."""
         u = self.unique().col
         return u.length - (0 if u.validity is None else int(u.length - K.aggregate(L.AGG_COUNT, u)[0]))
+
+    # ---- lookups (src/series.cpp:164-172, 341, 632-640; src/ndframe.h:276-282)
+    def _value_set(self, value_set):
+        """the value set as a column of this Series' dtype: Arrow casts the set; here where pdx_cast is exact, else an error"""
+        s = value_set.col if isinstance(value_set, Series) else value_set
+        if not isinstance(s, Column):
+            a = np.asarray(s)
+            host = {L.FLOAT64: np.float64, L.FLOAT32: np.float32, L.UINT64: np.uint64, L.INT32: np.int32}.get(self.col.dtype, np.int64)
+            if a.size and not np.array_equal(a.astype(host).astype(a.dtype), a, equal_nan=a.dtype.kind == "f"):
+                raise L.PdxError(L.INVALID, "is_in: the value set does not fit the Series' dtype")
+            return Column.from_numpy(a.astype(host), dtype=self.col.dtype)
+        if s.dtype == self.col.dtype:
+            return s
+        exact = {(L.INT32, L.INT64), (L.INT32, L.FLOAT64), (L.FLOAT32, L.FLOAT64)}
+        if (s.dtype, self.col.dtype) not in exact:
+            raise L.PdxError(L.INVALID, f"is_in: a value set of {K._DTYPE_NAMES[s.dtype]} has no exact cast to {K._DTYPE_NAMES[self.col.dtype]}")
+        return K.cast(s, self.col.dtype)
+
+    def is_in(self, value_set, skip_nulls=False):
+        """Series::is_in (src/series.cpp:632-636): bool Series without nulls over the same index; values match by bit pattern (pdx_is_in)"""
+        return self._wrap(K.is_in(self.col, self._value_set(value_set), skip_nulls))
+
+    def index_in(self, value_set, skip_nulls=False):
+        """Series::index_in (src/series.cpp:637-640): int32 position of the first occurrence in the value set, null without one (pdx_index_in)"""
+        return self._wrap(K.index_in(self.col, self._value_set(value_set), skip_nulls))
+
+    def index_of(self, value):
+        """NDFrame::index(Scalar) (src/ndframe.h:276-282): the first row equal to the value, -1 when there is none (`index` is the label
+        column here, hence the name)"""
+        return K.index(self.col, value.value if isinstance(value, Scalar) else value)
+
+    def argmin(self): return K.arg_extreme([self.col], False)[0]
+    def argmax(self): return K.arg_extreme([self.col], True)[0]
+
+    def _label_at(self, row, what):
+        if row < 0:  # the reference's GetScalar(-1) fails
+            raise L.PdxError(L.INDEX_ERROR, f"{what}: there is no valid value, index -1 is out of bounds")
+        if self.index is None:
+            return Scalar(row)
+        return Scalar(self.index.slice(row, 1).to_numpy()[0][0].item())
+
+    def idxMin(self):
+        """Series::idxMin (src/series.cpp:164-167): the index label at argmin()"""
+        return self._label_at(self.argmin(), "idxMin")
+
+    def idxMax(self):
+        return self._label_at(self.argmax(), "idxMax")
+
+    def dictionary_encode(self):
+        """Series::dictionary_encode (src/series.cpp:341): -> (indices Series int32 over the same index, dictionary Series)"""
+        codes, dic = K.dictionary_encode(self.col)
+        return self._wrap(codes), Series(dic, name=self.name)
 
     # ---- Series::where / take / operator[] (src/series.cpp:130-159, src/ndframe.cpp:347-350)
     def _index_col(self):
@@ -801,6 +873,15 @@ class DataFrame:
             if best is None or (best != best and x == x) or (x < best if kind == L.AGG_MIN else x > best):
                 best = x
         return Scalar(best)
+
+    def _idx_extreme(self, is_max, what):
+        """DataFrame::idxMin / idxMax (src/dataframe.cpp:496-512): column name -> index label at the column's argmin / argmax; one
+        pdx_arg_extreme call for the whole frame"""
+        rows = K.arg_extreme(self.cols, is_max)
+        return {nm: Series(c, index=self.index)._label_at(r, what) for nm, c, r in zip(self.names, self.cols, rows)}
+
+    def idxMin(self): return self._idx_extreme(False, "idxMin")
+    def idxMax(self): return self._idx_extreme(True, "idxMax")
 
     def min(self, axis=None, skip_null=True): return self._extreme(L.AGG_MIN) if axis is None else self._along("min", axis, L.AGG_MIN, skip_null)
     def max(self, axis=None, skip_null=True): return self._extreme(L.AGG_MAX) if axis is None else self._along("max", axis, L.AGG_MAX, skip_null)

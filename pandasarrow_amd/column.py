@@ -446,6 +446,66 @@ def is_unique(a: Column) -> bool:
         h.close()
 
 
+# ---------------------------------------------------------------- lookups (pdx_is_in ... pdx_dictionary_encode)
+def is_in(a: Column, value_set: Column, skip_nulls=False) -> Column:
+    """BOOL column without nulls: row i is set when a[i] is one of `value_set` (same dtype; matched by bit pattern) (pdx_is_in)"""
+    out = Column.empty(L.BOOL, a.length)
+    ca, cs, m = a.c(), value_set.c(), out.mut()
+    L.check(L.load().pdx_is_in(C.byref(ca), C.byref(cs), int(bool(skip_nulls)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def index_in(a: Column, value_set: Column, skip_nulls=False) -> Column:
+    """INT32 column: the position of a[i]'s first occurrence in `value_set`, null where there is none (pdx_index_in)"""
+    out = Column.empty(L.INT32, a.length, with_validity=True)
+    ca, cs, m = a.c(), value_set.c(), out.mut()
+    L.check(L.load().pdx_index_in(C.byref(ca), C.byref(cs), int(bool(skip_nulls)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def lookup_last_plan() -> dict:
+    """The plan of this thread's last is_in / index_in: {'plan': 'lds' | 'global' | 'empty', 'set_size': ..., 'slots': ...}."""
+    buf = C.create_string_buffer(256)
+    L.check(L.load().pdx_lookup_last_plan(buf, 256))
+    return dict(w.split("=", 1) for w in buf.value.decode().split() if "=" in w)
+
+
+def index(a: Column, value) -> int:
+    """The first valid row with a[row] == value (IEEE ==), -1 when there is none; None is the null scalar (pdx_index)"""
+    s = None
+    if value is not None:
+        s = L.PdxScalar(a.dtype, 1)
+        if a.dtype in (L.FLOAT64, L.FLOAT32):
+            s.v.f64 = float(value)
+        elif a.dtype == L.UINT64:
+            s.v.u64 = int(value)
+        else:
+            s.v.i64 = int(value)
+    row = C.c_int64(-1)
+    ca = a.c()
+    L.check(L.load().pdx_index(C.byref(ca), None if s is None else C.byref(s), C.byref(row), _stream()))
+    return int(row.value)
+
+
+def arg_extreme(cols, is_max=False):
+    """Per column the row of its smallest / largest valid value (the first on ties, NaN ignored), -1 when there is none: one launch for
+    all columns, which may differ in dtype (pdx_arg_extreme).  -> list of int"""
+    if not cols:
+        return []
+    rows = (C.c_int64 * len(cols))()
+    L.check(L.load().pdx_arg_extreme(int(bool(is_max)), _col_array(cols), len(cols), rows, _stream()))
+    return [int(r) for r in rows]
+
+
+def dictionary_encode(a: Column):
+    """-> (codes Column int32: null for a null row, dictionary Column of a's dtype: the distinct bit patterns in first-occurrence order)
+    (pdx_dictionary_encode)"""
+    codes, dic = Column.empty(L.INT32, a.length, with_validity=a.has_nulls()), Column.empty(a.dtype, a.length)
+    ca, mc, md = a.c(), codes.mut(), dic.mut()
+    L.check(L.load().pdx_dictionary_encode(C.byref(ca), C.byref(mc), C.byref(md), _stream()))
+    return codes._adopt(mc), dic._adopt(md)
+
+
 # ---------------------------------------------------------------- filter / take / concat
 def _col_array(cols):
     arr = (L.PdxColumn * len(cols))(*[c.c() for c in cols])

@@ -420,7 +420,10 @@ class Series {
   bool all() const { return bool_counts("all").second == 0; }
   bool any() const { return bool_counts("any").first > 0; }
   Series unique() const {
-    if (m_array.dtype == PDX_FLOAT64 || m_array.dtype == PDX_BOOL) throw std::runtime_error("unique: integer-like columns only through this facade");
+    // float64 (distinct bit patterns: 0.0 / -0.0, NaN payloads) and bool: the "values" of value_counts, which keys them as frequency_key() does
+    if (m_array.dtype == PDX_FLOAT64 || m_array.dtype == PDX_BOOL) return unique_by_frequency_key();
+    if (m_array.dtype == PDX_INT32 || m_array.dtype == PDX_FLOAT32)
+      throw std::runtime_error("unique: dtype int32 / float32 is not supported through this facade (the group-by takes no 4-byte keys; dictionary_encode() gives the distinct valid values)");
     auto ck = m_array.c();
     pdx_groupby* h = nullptr;
     ThrowOnFailure(pdx_groupby_create(&ck, nullptr, &h));
@@ -462,6 +465,7 @@ class Series {
   // Series::value_counts (src/dataframe.cpp:1093-1100): the distinct values (distinct bit patterns; a null is one entry) in first-occurrence
   // order and their counts -> frame with columns "values", "counts"
   inline DataFrame value_counts() const;
+  inline Series unique_by_frequency_key() const;
   // Series::is_unique (src/series.cpp:1243): unique().size() == size()
   bool is_unique() const {
     if (size() == 0) return true;
@@ -495,7 +499,90 @@ class Series {
     return {t, f};
   }
 
+  // the value set in this Series' dtype: Arrow casts the set; here only where the cast is exact (int64 -> float64, checked)
+  Array value_set_as_mine(const Array& set) const {
+    if (set.dtype == m_array.dtype) return set;
+    if (set.dtype == PDX_INT64 && m_array.dtype == PDX_FLOAT64) {
+      Array out = Array::Empty(PDX_FLOAT64, set.length, set.has_nulls());
+      auto cs = set.c();
+      auto m = out.mut();
+      ThrowOnFailure(pdx_cast_f64(&cs, /*checked=*/1, &m, nullptr));
+      out.null_count = m.null_count;
+      return out;
+    }
+    throw std::runtime_error("is_in: the value set has no exact cast to the Series' dtype");
+  }
+  Series set_lookup(bool index, const Series& value_set, bool skip_nulls) const {
+    Array set = value_set_as_mine(value_set.m_array);
+    Array out = Array::Empty(index ? PDX_INT32 : PDX_BOOL, size(), index);
+    auto ca = m_array.c(), cs = set.c();
+    auto m = out.mut();
+    ThrowOnFailure(index ? pdx_index_in(&ca, &cs, skip_nulls ? 1 : 0, &m, nullptr) : pdx_is_in(&ca, &cs, skip_nulls ? 1 : 0, &m, nullptr));
+    out.null_count = m.null_count;
+    return wrap(out);
+  }
+  Scalar label_at(int64_t row, const char* what) const {
+    if (row < 0) throw std::runtime_error(std::string(what) + ": there is no valid value, index -1 is out of bounds");  // GetScalar(-1)
+    return m_index ? Series(*m_index).at(row) : Scalar(row);
+  }
+
  public:
+  // ---- lookups (src/series.cpp:164-172, 341, 632-640; src/ndframe.h:276-282)
+  // is_in: bool Series without nulls; index_in: int32 position of the first occurrence in the value set, null without one.  Values match
+  // by bit pattern; the result keeps this Series' index.
+  Series is_in(const Series& value_set, bool skip_nulls = false) const { return set_lookup(false, value_set, skip_nulls); }
+  Series index_in(const Series& value_set, bool skip_nulls = false) const { return set_lookup(true, value_set, skip_nulls); }
+  // NDFrame::index(Scalar): the first row == value, -1 when there is none (a null value included)
+  int64_t index(const Scalar& value) const {
+    pdx_scalar v = value.s;
+    const bool col_float = m_array.dtype == PDX_FLOAT64 || m_array.dtype == PDX_FLOAT32;
+    if (v.is_valid && v.dtype != m_array.dtype) {
+      const bool val_float = v.dtype == PDX_FLOAT64 || v.dtype == PDX_FLOAT32;
+      if (m_array.dtype == PDX_BOOL || v.dtype == PDX_BOOL) throw std::runtime_error("index: the value's type differs from the Series'");
+      if (col_float && !val_float) {
+        if ((int64_t)(double)v.v.i64 != v.v.i64) return -1;  // (no double holds it, so no row does)
+        v.v.f64 = (double)v.v.i64;
+      } else if (!col_float && val_float) {
+        throw std::runtime_error("index: the value's type differs from the Series'");
+      }
+      // (float64 scalar, float32 column: the value travels widened; int64 scalar, int32 column: sign-extended -- pdx_index returns -1 for
+      // a value the column's width cannot hold)
+    }
+    v.dtype = m_array.dtype;
+    auto ca = m_array.c();
+    int64_t row = -1;
+    ThrowOnFailure(pdx_index(&ca, &v, &row, nullptr));
+    return row;
+  }
+  int64_t arg_extreme(bool is_max) const {
+    auto ca = m_array.c();
+    int64_t row = -1;
+    ThrowOnFailure(pdx_arg_extreme(is_max ? 1 : 0, &ca, 1, &row, nullptr));
+    return row;
+  }
+  int64_t argmin() const { return arg_extreme(false); }
+  int64_t argmax() const { return arg_extreme(true); }
+  // Series::idxMin / idxMax: the index label at argmin() / argmax(); throws when there is no valid value, as GetScalar(-1) does
+  Scalar idxMin() const { return label_at(argmin(), "idxMin"); }
+  Scalar idxMax() const { return label_at(argmax(), "idxMax"); }
+  // Series::dictionary_encode: (indices: int32 over this index, null for a null row; dictionary: distinct bit patterns, first-occurrence order)
+  std::pair<Series, Series> dictionary_encode() const {
+    Array codes = Array::Empty(PDX_INT32, size(), m_array.has_nulls()), dict = Array::Empty(m_array.dtype, size(), false);
+    auto ca = m_array.c();
+    auto mc = codes.mut(), md = dict.mut();
+    ThrowOnFailure(pdx_dictionary_encode(&ca, &mc, &md, nullptr));
+    codes.null_count = mc.null_count;
+    dict.length = md.length;
+    return {wrap(codes), Series(dict, std::nullopt, m_name)};
+  }
+  // the values of an int32 result (index_in, the codes of dictionary_encode) on the host, 0 under a null
+  std::vector<int32_t> values_i32() const {
+    if (m_array.dtype != PDX_INT32) throw std::runtime_error("values_i32: not an int32 Series");
+    std::vector<int32_t> out((size_t)size());
+    if (size()) ThrowOnFailure(pdx_to_host(out.data(), static_cast<const int32_t*>(m_array.values->ptr) + m_array.offset, (size_t)size() * 4, nullptr));
+    return out;
+  }
+
   // ---- where / take / operator[] (src/series.cpp:130-159, src/ndframe.cpp:347-350)
   Series where(const Series& mask) const {
     if (m_is_index) throw std::runtime_error("where() is not supported on an index Series");
@@ -1052,6 +1139,23 @@ class DataFrame {
     for (size_t i = 0; i < m_columns.size(); ++i) out[m_names[i]] = Series(m_columns[i]).quantile(q, interpolation, skip_nulls, min_count);
     return out;
   }
+  // DataFrame::idxMin / idxMax (src/dataframe.cpp:496-512): column name -> the index label at the column's argmin / argmax; one
+  // pdx_arg_extreme call for the whole frame (the columns may differ in dtype).  Throws when a column has no valid value.
+  std::map<std::string, Scalar> idx_extreme(bool is_max, const char* what) const {
+    std::map<std::string, Scalar> out;
+    if (m_columns.empty()) return out;
+    std::vector<pdx_column> cols;
+    for (auto& c : m_columns) cols.push_back(c.c());
+    std::vector<int64_t> rows(cols.size(), -1);
+    ThrowOnFailure(pdx_arg_extreme(is_max ? 1 : 0, cols.data(), (int)cols.size(), rows.data(), nullptr));
+    for (size_t i = 0; i < m_columns.size(); ++i) {
+      if (rows[i] < 0) throw std::runtime_error(std::string(what) + ": column " + m_names[i] + " has no valid value, index -1 is out of bounds");
+      out[m_names[i]] = m_index ? Series(*m_index).at(rows[i]) : Scalar(rows[i]);
+    }
+    return out;
+  }
+  std::map<std::string, Scalar> idxMin() const { return idx_extreme(false, "idxMin"); }
+  std::map<std::string, Scalar> idxMax() const { return idx_extreme(true, "idxMax"); }
   // NDFrame::sum on a frame (src/ndframe.h:329-335): every column (chunk) summed, totals added in column order
   Scalar sum() const {
     bool first = true, is_f = false;
@@ -1745,6 +1849,7 @@ inline DataFrame Series::value_counts() const {
   }
   return DataFrame({"values", "counts"}, {u, counts});
 }
+inline Series Series::unique_by_frequency_key() const { return Series(value_counts()["values"].m_array, std::nullopt, m_name); }
 inline Resampler DataFrame::resample(const std::string& rule, bool cr, bool lr) const { return pd::resample(*this, rule, cr, lr); }
 inline Resampler Series::resample(const std::string& rule, bool cr, bool lr) const { return pd::resample(*this, rule_to_ns(rule), cr, lr); }
 

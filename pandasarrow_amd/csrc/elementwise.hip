@@ -390,6 +390,18 @@ __global__ void __launch_bounds__(256) k_if_else_n(const uint8_t* __restrict__ c
 }
 
 // ---------------------------------------------------------------- functions of one column (pdx_unary, pdx_power, the casts)
+// negate / abs of a float touch the sign bit only, as Arrow's do: a signalling NaN stays signalling.  The bits go through an opaque
+// register so that they stay integer instructions: written as -x, hipcc selects v_pk_add_f32 (-x) + (-0) for two negations of the
+// row-per-lane loop, a floating-point add, which quiets the NaN (found by tests/test_gpu_elementwise.py, unary negate f32 in the row form).
+template <typename T>
+__device__ __forceinline__ T sign_bit(T x, bool clear) {
+  constexpr bits_t<T> kSign = bits_t<T>(1) << (sizeof(T) * 8 - 1);
+  bits_t<T> b = __builtin_bit_cast(bits_t<T>, x);
+  b = clear ? (b & ~kSign) : (b ^ kSign);
+  asm volatile("" : "+v"(b));
+  return __builtin_bit_cast(T, b);
+}
+
 constexpr int kPowerOp = 100;  // internal op codes: pdx_power, Arrow's (safe) cast, and the unchecked cast of pdx_cast_f64(checked = 0)
 constexpr int kCastOp = 101;
 constexpr int kPlainCastOp = 102;
@@ -397,11 +409,10 @@ template <int OP, typename TI, typename TO>
 __device__ __forceinline__ TO unary_one(TI x, int64_t i, double expo, const uint8_t* valid, int64_t voff, int64_t* bad) {
   using U = typename std::make_unsigned<typename std::conditional<is_float_t<TI>(), int, TI>::type>::type;
   if constexpr (OP == PDX_NEGATE) {
-    if constexpr (is_float_t<TI>()) return -x;
+    if constexpr (is_float_t<TI>()) return sign_bit(x, false);
     else return (TO)(U(0) - (U)x);  // wraps at TI's width
   } else if constexpr (OP == PDX_ABS) {
-    if constexpr (__is_same(TI, double)) return __builtin_fabs(x);
-    else if constexpr (__is_same(TI, float)) return __builtin_fabsf(x);
+    if constexpr (is_float_t<TI>()) return sign_bit(x, true);
     else if constexpr (std::is_unsigned<TI>::value) return x;
     else return x < 0 ? (TO)(U(0) - (U)x) : x;
   } else if constexpr (OP == PDX_SIGN) {

@@ -57,7 +57,7 @@ typedef enum pdx_dtype {
   PDX_UINT64 = 3,
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
-   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_mode, pdx_sort_indices, pdx_row_aggregate,
+   * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_mode, pdx_sort_indices, pdx_select_k, pdx_partition_nth, pdx_row_aggregate,
    * the lookups (pdx_is_in ... pdx_dictionary_encode)
    * and the selection / multiplexing calls (pdx_coalesce ... pdx_all_valid_mask); every other entry point returns
    * PDX_NOT_IMPLEMENTED naming the dtype (the group-by does not take 4-byte keys yet, so value_counts of such a column is refused too).  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
@@ -733,6 +733,40 @@ typedef struct pdx_sort_info {
   int32_t reserved;
 } pdx_sort_info;
 int pdx_sort_indices(const pdx_column* keys, int nkeys, const int* descending, pdx_mut_column* out_indices, pdx_sort_info* info, void* stream);
+
+/* ---------------------------------------------------------------- top-k and partition (Series::n_largest / n_smallest / nth_element)
+ * pdx_select_k: the first min(k, col.length) entries of what pdx_argsort(col, ascending) writes, bit for bit, without sorting the column
+ * (the reference's n_largest / n_smallest, src/series.cpp:1211-1229, are sort + Slice).  So: STABLE in both orders (equal values keep
+ * their row order; -0.0 == 0.0), NaN rows behind every number and null rows behind the NaNs in BOTH orders; a k beyond the count of
+ * numbers continues with the first NaN rows in row order, then the first null rows in row order.
+ *   col: int64 / uint64 / float64 / timestamp[ns] / int32 / float32 (bool: PDX_NOT_IMPLEMENTED), <= 2^31-1 rows, offset and validity
+ *   honoured; k < 0: PDX_INVALID; out_indices: PDX_UINT64 without validity, capacity >= min(k, length); its length is set to that value
+ *   and nothing beyond it is written.
+ * Plans (pdx_select_k_last_plan, diagnostic, this thread's last pdx_select_k: "plan=select|sort|empty k=... rows=... levels=..."):
+ *   empty   k == 0 or an empty column: nothing is launched.
+ *   select  the radix select of pdx_quantile finds the key T at the k-th place among the numbers (levels = histogram levels it took);
+ *           one counting read, a scan and one writing read collect the rows that beat T and the first k - (their count) rows equal to
+ *           T in row order (+ the first NaN / null rows when k exceeds the numbers); only those k (key, row) pairs are sorted.
+ *   sort    k >= length, or k above the crossover fraction of the rows (a measured constant): one single-key
+ *           pdx_sort_indices, the first k indices copied out.
+ *   PDX_SELECT_K_PLAN=select|sort (environment, read per call) forces a plan wherever it is legal (select needs 0 < k < length).
+ *
+ * pdx_partition_nth: Series::nth_element (src/series.cpp:973-976, CallFunction("partition_nth_indices", PartitionNthOptions{pivot})).
+ * DEVIATION, on purpose: Arrow's output is whatever std::nth_element left behind (its null rows are not even in row order), so this call
+ * is NOT bit-identical to Arrow; it is defined by its own contract.  With m the count of numbers and p = min(pivot, m):
+ *   - out_indices is a permutation of 0 .. length-1;
+ *   - every number in places [0, p) is <= every number in places [p, m);
+ *   - if pivot < m, the row at place pivot holds the value pdx_argsort(col, 1) puts at place pivot;
+ *   - the NaN rows follow in places [m, m + nan), then the null rows;
+ *   - the layout is deterministic: with T the key at rank min(pivot, m - 1) of the numbers (pivot >= m: the largest key), the rows with
+ *     key < T in row order, the rows with key == T in row order, the rows with key > T in row order, the NaN rows in row order, the
+ *     null rows in row order.
+ * It runs the same select, one counting read and one scatter read, and sorts nothing.  pivot == length is legal (as in Arrow);
+ * pivot < 0 or pivot > length: PDX_INVALID (Arrow happens to accept a negative pivot; that is not mirrored).  Same dtypes and limits as
+ * pdx_select_k; out_indices: PDX_UINT64 without validity, capacity >= length. */
+int pdx_select_k(const pdx_column* col, int64_t k, int ascending, pdx_mut_column* out_indices, void* stream);
+int pdx_partition_nth(const pdx_column* col, int64_t pivot, pdx_mut_column* out_indices, void* stream);
+int pdx_select_k_last_plan(char* buf, size_t buf_len);
 
 /* ---------------------------------------------------------------- concat (rows)
  * Replaces arrow::ConcatenateTables + CombineChunksToBatch at src/concat.cpp:152-154 for same-dtype parts

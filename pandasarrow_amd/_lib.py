@@ -213,6 +213,9 @@ ABI_SYMBOLS = {
     "pdx_index_intersection": (C.c_int, [_COL, _COL, _MUT, _P]),
     "pdx_argsort": (C.c_int, [_COL, C.c_int, _MUT, _P]),
     "pdx_sort_indices": (C.c_int, [_COL, C.c_int, C.POINTER(C.c_int), _MUT, C.POINTER(PdxSortInfo), _P]),
+    "pdx_select_k": (C.c_int, [_COL, C.c_int64, C.c_int, _MUT, _P]),
+    "pdx_partition_nth": (C.c_int, [_COL, C.c_int64, _MUT, _P]),
+    "pdx_select_k_last_plan": (C.c_int, [C.c_char_p, C.c_size_t]),
     "pdx_reindex_indices": (C.c_int, [_COL, _COL, _MUT, _P]),
 }
 

@@ -546,13 +546,22 @@ class Series:
         outs = K.take([self.col, ix], idx)
         return Series(outs[0], index=outs[1], name=self.name)
 
+    def _top(self, n, ascending):
+        """the first n rows of sort(ascending), values AND index, by pdx_select_k (all of them when size() < n)"""
+        idx = K.select_k(self.col, n, ascending)
+        outs = K.take([self.col, self._explicit_index()], idx)
+        return Series(outs[0], index=outs[1], name=self.name)
+
     def n_largest(self, n):
-        s = self.sort(False)
-        return s if s.size() < n else Series(s.col.slice(0, n), index=s.index.slice(0, n), name=self.name)
+        return self._top(n, False)
 
     def n_smallest(self, n):
-        s = self.sort(True)
-        return s if s.size() < n else Series(s.col.slice(0, n), index=s.index.slice(0, n), name=self.name)
+        return self._top(n, True)
+
+    def nth_element(self, n=0):
+        """Series::nth_element (src/series.cpp:973-976): "partition_nth_indices" -> uint64 indices with the index re-attached.  The order
+        inside the parts is pdx_partition_nth's deterministic one, not Arrow's."""
+        return self._wrap(K.partition_nth(self.col, n))
 
     def resample(self, rule, closed_right=False, label_right=False, origin=L.ORIGIN_START_DAY, offset_ns=0, origin_custom_ns=0):
         return DataFrame({self.name or "0": self}, index=self.index).resample(rule, closed_right, label_right, origin, offset_ns, origin_custom_ns)

@@ -719,6 +719,32 @@ def sort_indices(keys, descending=None, with_info=False):
     return (out, (info.rounds, info.key_bits, info.passes)) if with_info else out
 
 
+def select_k(a: Column, k: int, ascending=True) -> Column:
+    """the first min(k, a.length) uint64 take indices of argsort(a, ascending), without sorting the column (pdx_select_k)"""
+    out = Column.empty(L.UINT64, max(0, min(int(k), a.length)))
+    m = out.mut()
+    ca = a.c()
+    L.check(L.load().pdx_select_k(C.byref(ca), int(k), int(bool(ascending)), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def partition_nth(a: Column, pivot: int) -> Column:
+    """uint64 indices that partition a around the value of rank `pivot`: smaller keys, equal keys, larger keys, NaN rows, null rows, each
+    in row order (pdx_partition_nth; deterministic, not Arrow's std::nth_element order)"""
+    out = Column.empty(L.UINT64, a.length)
+    m = out.mut()
+    ca = a.c()
+    L.check(L.load().pdx_partition_nth(C.byref(ca), int(pivot), C.byref(m), _stream()))
+    return out._adopt(m)
+
+
+def select_k_last_plan() -> dict:
+    """The plan of this thread's last select_k: {'plan': 'select' | 'sort' | 'empty', 'k': ..., 'rows': ..., 'levels': ...}."""
+    buf = C.create_string_buffer(256)
+    L.check(L.load().pdx_select_k_last_plan(buf, 256))
+    return dict(w.split("=", 1) for w in buf.value.decode().split() if "=" in w)
+
+
 def reindex_indices(old_index: Column, new_index: Column) -> Column:
     """int64 take indices (LAST position of every new label in old_index, null where absent)."""
     out = Column.empty(L.INT64, new_index.length, with_validity=True)

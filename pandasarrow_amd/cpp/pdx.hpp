@@ -646,8 +646,18 @@ class Series {
     // (the implicit 0..n-1 index taken by the sort indices is the sort indices)
     return Series(outs[0], m_index ? outs[1] : idx, m_name);
   }
-  Series n_largest(int n) const { return sort(false).head(n); }
-  Series n_smallest(int n) const { return sort(true).head(n); }
+  // n_largest / n_smallest: the first n rows of sort(order) by pdx_select_k (no full sort for a small n; all rows when size() <= n)
+  Series n_largest(int n) const { return top(n, false); }
+  Series n_smallest(int n) const { return top(n, true); }
+  // Series::nth_element (src/series.cpp:973-976, "partition_nth_indices"): the order inside the parts is pdx_partition_nth's
+  // deterministic one (smaller, equal, larger, NaN, null; each in row order), not what Arrow's std::nth_element leaves behind
+  Series nth_element(int n = 0) const {
+    Array idx = Array::Empty(PDX_UINT64, size(), false);
+    auto ca = m_array.c();
+    auto mi = idx.mut();
+    ThrowOnFailure(pdx_partition_nth(&ca, n, &mi, nullptr));
+    return wrap(idx);
+  }
   Series head(int64_t n) const {  // array()->Slice(0, n): zero copy
     if (size() <= n) return *this;
     Series s = *this;
@@ -812,6 +822,14 @@ class Series {
   }
 
  private:
+  Series top(int n, bool ascending) const {
+    Array idx = Array::Empty(PDX_UINT64, std::max<int64_t>(0, std::min<int64_t>(n, size())), false);
+    auto ca = m_array.c();
+    auto mi = idx.mut();
+    ThrowOnFailure(pdx_select_k(&ca, n, ascending ? 1 : 0, &mi, nullptr));
+    auto outs = run_take(columns_with_index(), idx);
+    return Series(outs[0], m_index ? outs[1] : idx, m_name);
+  }
   // ReturnSeriesOrThrowOnError (src/series.cpp:1364-1384): equal length -> same index; the result name is reset to ""
   Series wrap(Array a) const { return Series(std::move(a), m_index, ""); }
   // ... an empty result or no index -> no index; a shorter result keeps the LAST `length` labels (idx->Slice(indexLength - arrayLength))

@@ -57,14 +57,17 @@ __global__ void __launch_bounds__(1024) k_sample_key_range(const long long* __re
     out[blockIdx.x].any = any;
   }
 }
+// WRITE_SLOTS = false: the tail kernel that follows walks all tiles from 0 and writes every row's slot itself (the LDS tail, and the
+// global-bitmap tail when it also computes the key range), so only first[] is wanted from the prefix
+template <bool WRITE_SLOTS>
 __global__ void __launch_bounds__(256) k_dense_slots(const long long* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t off,
                                                      int64_t n, long long mn, unsigned int mask, unsigned int range, unsigned int* first,
                                                      uint32_t* __restrict__ slot_of_row) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     unsigned int s = range;  // the null key's slot
-    if (!valid || bit_get(valid, off + i)) s = dense_slot_of(keys[i], mn, mask);
-    slot_of_row[i] = s;
+    if (!valid || bit_get(valid, off + i)) s = dense_slot_of(ld_stream<kStreamDenseKeys>(keys + i), mn, mask);
+    if constexpr (WRITE_SLOTS) st_stream<kStreamDenseSlots>(slot_of_row + i, s);
     // only the first lane of every slot present in the wave needs the atomic (lanes hold ascending rows): with a handful of
     // distinct keys tens of thousands of in-flight atomicMin's on one word otherwise serialise in the L2 (measured 5.8 ms)
     const bool want = (unsigned int)i < first[s];
@@ -208,6 +211,10 @@ __global__ void __launch_bounds__(kSortBlock) k_dense_slots_tail_hist(const long
 
 // Same, for domains of <= 2^20 slots: persistent workgroups (one per CU) keep the whole `seen` bitmap in LDS (128 KB), so the
 // per-row bitmap lookup is an LDS read instead of a random TA/L1 access; one wave owns one tile at a time (wave-private histogram).
+// 1: full tiles of a non-null, 16-byte aligned key column take four rows per lane (16-byte loads and stores); 0: one row per lane always
+#ifndef PDX_DENSE_WIDE
+#define PDX_DENSE_WIDE 1
+#endif
 constexpr int kDenseLdsWords = 32768;
 constexpr int kDenseLdsBlock = 1024;
 template <int BITS>
@@ -233,52 +240,89 @@ __global__ void __launch_bounds__(kDenseLdsBlock) k_dense_slots_tail_hist_lds(co
   long long kmn = 0x7FFFFFFFFFFFFFFFll, kmx = (long long)0x8000000000000000ull;
   int any = 0;
   bool few = true;  // wave-uniform
+  // one row once its slot is known: the histogram count and, where the bitmap has not seen the slot, the first-row protocol
+  auto count_and_track = [&](bool in, unsigned int sl, int64_t i) {
+    const uint32_t w = lseen[sl >> 5];
+    // few distinct digits (few distinct keys): lanes adding to the same LDS word serialise, so peel the rows off digit by
+    // digit and add each digit's count once.  `few` is dropped for good the first time a step needs more than 4 rounds (a round costs about as much as a 4-way conflict).
+    const unsigned int d = sl & (R - 1);
+    if (few) {
+      uint64_t rem = __ballot(in);
+      int rounds = 0;
+      while (rem && rounds < 4) {
+        const int leader = __ffsll((unsigned long long)rem) - 1;
+        const unsigned int dl = (unsigned int)__shfl((int)d, leader, 64);
+        const uint64_t grp = __ballot(in && d == dl) & rem;
+        if (lane == leader) atomicAdd(&lh[wave][dl], (uint32_t)__popcll(grp));
+        rem &= ~grp;
+        ++rounds;
+      }
+      if (rem) {
+        few = false;
+        if ((rem >> lane) & 1) atomicAdd(&lh[wave][d], 1u);
+      }
+    } else if (in) {
+      atomicAdd(&lh[wave][d], 1u);
+    }
+    if (in && !((w >> (sl & 31)) & 1u) && i >= track_from) {
+      if ((unsigned int)i < first[sl]) atomicMin(&first[sl], (unsigned int)i);
+    }
+  };
+  // wide form: nothing below depends on which lane holds which row, so where the layout allows 16-byte accesses (no validity bitmap,
+  // keys and slots on 16 bytes; tiles are 4096 rows, so the tile base keeps the pointers' alignment) a lane owns four consecutive rows
+  const bool can_wide = PDX_DENSE_WIDE && !valid && ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(slot_of_row)) & 15) == 0;
   for (int64_t tile = tile0 + (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += nw) {
     const int64_t base = tile * kSortTile;
+    if (can_wide && base + kSortTile <= n) {
 #pragma unroll 1
-    for (int c = 0; c < kSortTile / 1024; ++c) {
-      long long k[16];
+      for (int c = 0; c < kSortTile / 1024; ++c) {
+        // rows base + c * 1024 + u * 256 + 4 * lane + {0..3}: two 16-byte key loads and one 16-byte slot store per u
+        const i64x2* kp = reinterpret_cast<const i64x2*>(keys + base + c * 1024) + 2 * lane;
+        u32x4* sp = reinterpret_cast<u32x4*>(slot_of_row + base + c * 1024) + lane;
+        i64x2 k2[8];
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        int64_t i = base + c * 1024 + u * 64 + lane;
-        k[u] = i < n ? keys[i] : 0;
+        for (int u = 0; u < 4; ++u) {
+          k2[2 * u] = ld_stream<kStreamDenseKeys>(kp + u * 128);
+          k2[2 * u + 1] = ld_stream<kStreamDenseKeys>(kp + u * 128 + 1);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const long long k4[4] = {k2[2 * u].x, k2[2 * u].y, k2[2 * u + 1].x, k2[2 * u + 1].y};
+          u32x4 out;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const unsigned int sl = dense_slot_of(k4[j], mn, mask);
+            kmn = k4[j] < kmn ? k4[j] : kmn;
+            kmx = k4[j] > kmx ? k4[j] : kmx;
+            out[j] = sl;
+            count_and_track(true, sl, base + c * 1024 + u * 256 + 4 * lane + j);
+          }
+          st_stream<kStreamDenseSlots>(sp + u * 64, out);
+        }
       }
+      any = 1;
+    } else {
+#pragma unroll 1
+      for (int c = 0; c < kSortTile / 1024; ++c) {
+        long long k[16];
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        int64_t i = base + c * 1024 + u * 64 + lane;
-        const bool in = i < n;
-        unsigned int sl = range;
-        if (in && (!valid || bit_get(valid, off + i))) {
-          sl = dense_slot_of(k[u], mn, mask);
-          kmn = k[u] < kmn ? k[u] : kmn;
-          kmx = k[u] > kmx ? k[u] : kmx;
-          any = 1;
+        for (int u = 0; u < 16; ++u) {
+          int64_t i = base + c * 1024 + u * 64 + lane;
+          k[u] = i < n ? ld_stream<kStreamDenseKeys>(keys + i) : 0;
         }
-        const uint32_t w = lseen[sl >> 5];
-        if (in) slot_of_row[i] = sl;
-        // few distinct digits (few distinct keys): lanes adding to the same LDS word serialise, so peel the rows off digit by
-        // digit and add each digit's count once.  `few` is dropped for good the first time a step needs more than 4 rounds (a round costs about as much as a 4-way conflict).
-        const unsigned int d = sl & (R - 1);
-        if (few) {
-          uint64_t rem = __ballot(in);
-          int rounds = 0;
-          while (rem && rounds < 4) {
-            const int leader = __ffsll((unsigned long long)rem) - 1;
-            const unsigned int dl = (unsigned int)__shfl((int)d, leader, 64);
-            const uint64_t grp = __ballot(in && d == dl) & rem;
-            if (lane == leader) atomicAdd(&lh[wave][dl], (uint32_t)__popcll(grp));
-            rem &= ~grp;
-            ++rounds;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+          int64_t i = base + c * 1024 + u * 64 + lane;
+          const bool in = i < n;
+          unsigned int sl = range;
+          if (in && (!valid || bit_get(valid, off + i))) {
+            sl = dense_slot_of(k[u], mn, mask);
+            kmn = k[u] < kmn ? k[u] : kmn;
+            kmx = k[u] > kmx ? k[u] : kmx;
+            any = 1;
           }
-          if (rem) {
-            few = false;
-            if ((rem >> lane) & 1) atomicAdd(&lh[wave][d], 1u);
-          }
-        } else if (in) {
-          atomicAdd(&lh[wave][d], 1u);
-        }
-        if (in && !((w >> (sl & 31)) & 1u) && i >= track_from) {
-          if ((unsigned int)i < first[sl]) atomicMin(&first[sl], (unsigned int)i);
+          if (in) st_stream<kStreamDenseSlots>(slot_of_row + i, sl);
+          count_and_track(in, sl, i);
         }
       }
     }

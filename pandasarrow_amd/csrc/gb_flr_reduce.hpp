@@ -272,8 +272,8 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
         // (rows behind the tile's end read its last row instead of branching around the load: they are never ranked or staged)
         const int r = wave * (64 * kFlrItems) + q * 64 + lane;
         const int rr = r < rows ? r : rows - 1;
-        key[q] = keys[t0 + rr];
-        val[q] = vals[t0 + rr];
+        key[q] = ld_stream<kStreamFlrTile>(keys + t0 + rr);
+        val[q] = ld_stream<kStreamFlrTile>(vals + t0 + rr);
       }
     };
     load_tile(s);

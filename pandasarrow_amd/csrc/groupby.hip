@@ -243,8 +243,17 @@ int pdx_groupby_create(const pdx_column* key, void* stream, pdx_groupby** out) {
     // rows that go through the full first-row protocol before the tail's bitmap is taken: a slot unseen by then costs one global atomic per
     // later row of its key.  16 rows per slot leave e^-16 of uniformly spread keys unseen; below 2^29 rows 8 per slot (e^-8 = 3e-4 of the
     // slots, a few 10^4 atomics) -- the prefix pass is the slow one (60 Grows/s: a random read of first[] per row) and at an 8-GPU shard's
-    // size 16 per slot was 13 % of the rows, 0.28 ms of a 0.84 ms create
-    const int64_t per_slot = [n] { const char* e = getenv("PDX_DENSE_PREFIX_PER_SLOT"); return e && atoi(e) > 0 ? (int64_t)atoi(e) : (n < ((int64_t)1 << 29) ? 8 : 16); }();
+    // size 16 per slot was 13 % of the rows, 0.28 ms of a 0.84 ms create.
+    // From 2^29 rows on, domains whose bitmap fits the LDS tail (<= 2^20 slots) take 4 per slot: an unseen slot there costs a read of the
+    // cache-resident first[] per later row and an atomic only for the first of them.  Measured at 1e9 rows / 1e6 keys, the slot kernels
+    // per step over five alternated runs each: 16 -> 2.51-2.57 ms, 8 -> 2.46-2.52 ms, 4 -> 2.37-2.45 ms (at 1e5 keys the 2^22-row floor
+    // below decides and the three are the same 2.35 ms).  Larger domains (global bitmap, first[] not cache resident) keep 16.
+    const int64_t per_slot = [n, this_nslots = nslots] {
+      const char* e = getenv("PDX_DENSE_PREFIX_PER_SLOT");
+      if (e && atoi(e) > 0) return (int64_t)atoi(e);
+      if (n < ((int64_t)1 << 29)) return (int64_t)8;
+      return ((this_nslots + 31) >> 5) <= kDenseLdsWords ? (int64_t)4 : (int64_t)16;
+    }();
     int64_t prefix = std::min<int64_t>(n, std::max<int64_t>((int64_t)1 << 22, per_slot * nslots));
     prefix = std::min<int64_t>(n, round_up(prefix, kSortTile));
     const bool fuse = bits0 >= 4 && bits0 <= 8;
@@ -271,8 +280,13 @@ int pdx_groupby_create(const pdx_column* key, void* stream, pdx_groupby** out) {
     }
     {
       PDX_PROFILE("dense_slots", st);
-      hipLaunchKernelGGL(k_dense_slots, dim3(grid_for(prefix, 256, 8)), dim3(256), 0, st, keys, valid, key->offset, prefix, mn, mask, null_slot,
-                         dense_first, gb->slot_of_row);
+      // (a tail that walks all tiles from 0 rewrites every slot: the prefix then leaves slot_of_row alone)
+      if (prefix < n && fuse && (lds_bitmap || range_out))
+        hipLaunchKernelGGL(k_dense_slots<false>, dim3(grid_for(prefix, 256, 8)), dim3(256), 0, st, keys, valid, key->offset, prefix, mn, mask, null_slot,
+                           dense_first, gb->slot_of_row);
+      else
+        hipLaunchKernelGGL(k_dense_slots<true>, dim3(grid_for(prefix, 256, 8)), dim3(256), 0, st, keys, valid, key->offset, prefix, mn, mask, null_slot,
+                           dense_first, gb->slot_of_row);
       if (prefix < n) {
         uint32_t* seen = s.get<uint32_t>((size_t)nwords);
         if (s.failed) return PDX_OOM;

@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "pdx_common.hpp"
 #include "scan.hpp"
+#include "stream_io.hpp"
 
 namespace pdx {
 
@@ -58,11 +59,11 @@ __global__ void __launch_bounds__(kSortBlock) k_radix_hist(const K* __restrict__
   int64_t base = (int64_t)blockIdx.x * kSortTile;
   if (base + kSortTile <= n && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
     // full tile: 16-byte loads, all of them in flight before the LDS atomics
-    const uint4* k4 = reinterpret_cast<const uint4*>(keys + base);
-    uint4 v[NV];
+    const u32x4* k4 = reinterpret_cast<const u32x4*>(keys + base);
+    u32x4 v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k)
-      if (NV4 % kSortBlock == 0 || k * kSortBlock + (int)threadIdx.x < NV4) v[k] = k4[k * kSortBlock + threadIdx.x];
+      if (NV4 % kSortBlock == 0 || k * kSortBlock + (int)threadIdx.x < NV4) v[k] = ld_stream<kStreamHistKeys>(k4 + k * kSortBlock + threadIdx.x);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       if (!(NV4 % kSortBlock == 0 || k * kSortBlock + (int)threadIdx.x < NV4)) continue;
@@ -84,7 +85,7 @@ __global__ void __launch_bounds__(kSortBlock) k_radix_hist(const K* __restrict__
 #pragma unroll
     for (int k = 0; k < kSortItems; ++k) {
       int64_t i = base + k * kSortBlock + threadIdx.x;
-      if (i < n) wave_hist_add(h, ((uint32_t)keys[i] >> shift) & (R - 1), cand);
+      if (i < n) wave_hist_add(h, ((uint32_t)ld_stream<kStreamHistKeys>(keys + i) >> shift) & (R - 1), cand);
     }
   }
   __syncthreads();
@@ -326,20 +327,22 @@ __device__ __forceinline__ void radix_scatter_body(const K* __restrict__ keys_in
         int64_t row = tile_base + r;
         val[s] = (V)row | ((iota.valid && !bit_get(iota.valid, iota.off + row)) ? (V)0x80000000u : (V)0);
       } else {
-        val[s] = vals_in[tile_base + r];
+        val[s] = ld_stream<kStreamScatVals>(vals_in + tile_base + r);
       }
     }
   }
   // byte digits: one 16-byte load per lane, transposed through the (still unused) key staging area -- sixteen 1-byte loads per
   // lane cost as many memory instructions as sixteen 4-byte ones (measured: 4.3 ms per 1e9 rows for 5 GB moved)
+  // (4-byte keys through the same staging -- four 16-byte loads per lane instead of sixteen dword loads -- measured no faster:
+  //  DESIGN.md, "Stream access policy")
   bool bytes_staged = false;
   if constexpr (sizeof(K) < 4) {
     if (tile_rows == kSortTile && (reinterpret_cast<uintptr_t>(keys_in) & 15) == 0) {
       // a wave's 64 * kScatItems narrow keys = 4 * kScatItems * sizeof(K) lanes x 16 bytes
       constexpr int NV = 4 * kScatItems * (int)sizeof(K);
       for (int j = lane; j < NV; j += 64) {
-        const uint4 v = reinterpret_cast<const uint4*>(keys_in + tile_base + wave * (64 * kScatItems))[j];
-        reinterpret_cast<uint4*>(skeys)[wave * NV + j] = v;
+        const u32x4 v = ld_stream<kStreamScatKeys>(reinterpret_cast<const u32x4*>(keys_in + tile_base + wave * (64 * kScatItems)) + j);
+        reinterpret_cast<u32x4*>(skeys)[wave * NV + j] = v;
       }
       __builtin_amdgcn_wave_barrier();
       bytes_staged = true;
@@ -350,7 +353,7 @@ __device__ __forceinline__ void radix_scatter_body(const K* __restrict__ keys_in
     int r = wave * (64 * kScatItems) + s * 64 + lane;
     if constexpr (PAYLOAD_DIGIT) key[s] = r < tile_rows ? (uint32_t)((unsigned long long)val[s] >> 32) : 0u;
     else if (bytes_staged) key[s] = reinterpret_cast<const K*>(skeys)[r];  // (key r of the tile: waves are laid out back to back)
-    else key[s] = r < tile_rows ? (uint32_t)keys_in[tile_base + r] : 0u;
+    else key[s] = r < tile_rows ? (uint32_t)ld_stream<kStreamScatKeys>(keys_in + tile_base + r) : 0u;
   }
   if constexpr (FLAGS && !IOTA && sizeof(K) == 4) {
     if (iota.valid) {
@@ -430,13 +433,13 @@ __device__ __forceinline__ void radix_scatter_body(const K* __restrict__ keys_in
     if (WRITE_KEYS) {
       if constexpr (FLAGS) {
         constexpr int FI = 8 * (int)sizeof(K) - 1, FO = 8 * (int)sizeof(KO) - 1;
-        keys_out[g] = (KO)(((k & ((1u << FI) - 1u)) >> drop) | ((k >> FI) << FO));
+        st_stream<kStreamScatOut>(keys_out + g, (KO)(((k & ((1u << FI) - 1u)) >> drop) | ((k >> FI) << FO)));
       } else {
-        keys_out[g] = (KO)(k >> drop);
+        st_stream<kStreamScatOut>(keys_out + g, (KO)(k >> drop));
       }
     }
-    vals_out[g] = v;
-    if constexpr (EMIT_ROWS) rows_out[g] = (uint32_t)(tile_base + ((k >> 8) & 0xFFFu)) | (k & 0x80000000u);
+    st_stream<kStreamScatOut>(vals_out + g, v);
+    if constexpr (EMIT_ROWS) st_stream<kStreamScatOut>(rows_out + g, (uint32_t)(tile_base + ((k >> 8) & 0xFFFu)) | (k & 0x80000000u));
   };
   if constexpr (!HALF) {
     // contiguous runs per digit -> coalesced stores

@@ -58,7 +58,7 @@ typedef enum pdx_dtype {
   PDX_TIMESTAMP_NS = 4, /* int64 nanoseconds since epoch */
   /* 4 bytes per value (`offset` still counts elements).  Accepted by pdx_binary, pdx_compare, pdx_if_else, pdx_unary (not
    * pdx_power), pdx_cast, pdx_aggregate, pdx_filter, pdx_take, pdx_scatter, pdx_concat, pdx_cumulative, pdx_fill_null, pdx_shift, pdx_quantile, pdx_mode, pdx_sort_indices, pdx_select_k, pdx_partition_nth, pdx_row_aggregate,
-   * the lookups (pdx_is_in ... pdx_dictionary_encode)
+   * the lookups (pdx_is_in ... pdx_dictionary_encode), pdx_join_create (PDX_INT32 keys)
    * and the selection / multiplexing calls (pdx_coalesce ... pdx_all_valid_mask); every other entry point returns
    * PDX_NOT_IMPLEMENTED naming the dtype (the group-by does not take 4-byte keys yet, so value_counts of such a column is refused too).  In a pdx_scalar an INT32 value is held sign-extended in v.i64, a FLOAT32 value
    * widened (exactly) in v.f64. */
@@ -562,6 +562,52 @@ int pdx_lookup_last_plan(char* buf, size_t buf_len);
 int pdx_index(const pdx_column* a, const pdx_scalar* value /* NULL: the null scalar */, int64_t* out_row /* host */, void* stream);
 int pdx_arg_extreme(int is_max, const pdx_column* cols, int ncols, int64_t* out_rows /* host, ncols */, void* stream);
 int pdx_dictionary_encode(const pdx_column* a, pdx_mut_column* out_codes, pdx_mut_column* out_dict, void* stream);
+
+/* ---------------------------------------------------------------- join: hash equi-join of two frames on one key column
+ * The reference's README lists "merging and joining" and implements neither (its column-wise pd::concat aligns on UNIQUE labels only), so
+ * there is no call site to cite: the facades' DataFrame::merge / join are built on these calls.  The result size depends on the data, so the
+ * join lives in a handle: pdx_join_create matches the keys and knows the row count, pdx_join_indices writes the result as two PDX_INT64
+ * columns of TAKE INDICES into the left and the right frame, made to be fed to pdx_take (whose null index gives a null row).
+ *   keys    : one column per side, PDX_INT64, PDX_UINT64, PDX_TIMESTAMP_NS or PDX_INT32, the same dtype on both sides (PDX_INVALID
+ *             otherwise: cast one side first).  PDX_FLOAT64, PDX_FLOAT32 and PDX_BOOL return PDX_NOT_IMPLEMENTED naming the dtype (no rule
+ *             for float equality is decided here).  Any offset, validity at any bit offset, null_count -1, a column without validity is
+ *             all valid.  At most 2^31-1 rows per side (the group-by handle's limit; PDX_NOT_IMPLEMENTED beyond); the OUTPUT row count is
+ *             an int64 and may exceed 2^31.  An empty side is not an error.  Every refusal happens before anything is launched.
+ *   match   : keys match by value.  A NULL KEY MATCHES NOTHING, not even another null: the rule of Arrow's hash join (Acero, with its
+ *             default JoinKeyCmp::EQ) and of SQL.  pandas' merge differs: it matches null keys with each other.
+ *   how     : pdx_join_how.  The row order is fully defined:
+ *             INNER  rows ordered by left row; the matches of one left row by ascending right row.
+ *             LEFT   the same, and a left row without a match (a null key included) appears once, with a NULL right index.
+ *             OUTER  LEFT, followed by the right rows that no left row matched (null-key rows among them) in right row order, each with
+ *                    a NULL left index.
+ *             SEMI   the left rows with at least one match, ANTI those without (null keys included), each once, in left order; there is
+ *                    no right output.
+ *             (A RIGHT join is a LEFT join with the sides swapped; the facades do that.)
+ *   outputs : pdx_join_indices: out_left / out_right are PDX_INT64 of capacity >= pdx_join_rows; a smaller capacity, another dtype or a
+ *             missing buffer returns PDX_INVALID before anything is written.  out_right->validity is required unless how is INNER,
+ *             out_left->validity for OUTER (PDX_INVALID otherwise, whether or not a null occurs); where a validity buffer is given and no
+ *             null can occur its bits are set.  For SEMI / ANTI out_right must be NULL (PDX_INVALID otherwise: there is nothing to
+ *             write).  On return both lengths are the row count and null_count is exact; value bytes under a null index are zero; rows,
+ *             bytes and validity bits beyond the result length are untouched.  Deterministic: the same bytes on any stream and run.
+ *             pdx_join_indices may be called more than once on a handle.
+ *   how it runs: the right side is grouped by the group-by handle (distinct keys in first-occurrence order, pdx_groupby_groupings' rows of
+ *             every key in row order; an int32 key is zero-extended to 8 bytes first); the distinct keys go into the lookups'
+ *             open-addressing table (load factor <= 0.5), probed from a copy in LDS up to 2048 distinct keys (PDX_LOOKUP_LDS_MAX lowers
+ *             the bound) and in global memory beyond; one pass over the left keys writes every row's match list and output count; an
+ *             exclusive scan gives every left row its first output row.  pdx_join_create reads the totals back once (its only host wait
+ *             beside those of the group-by calls) and, for SEMI / ANTI and the OUTER tail, compacts the selected rows.
+ *             pdx_join_indices is asynchronous on `stream`: its kernel is output-parallel -- a workgroup owns 2048 consecutive output
+ *             rows and finds the left rows that cover them by a search of the offsets -- so one hot key is written by as many workgroups
+ *             as its matches fill, and left rows without output cost nothing.  The handle holds 16 bytes per left row and 8 per right row.
+ *   pdx_join_last_plan (diagnostic; tests assert it): "plan=lds|global|empty build_rows=<right rows> distinct=<groups of the right key, the
+ *             null key counting as one> out_rows=<pdx_join_rows>"; empty: the right side has no rows. */
+typedef enum pdx_join_how { PDX_JOIN_INNER = 0, PDX_JOIN_LEFT = 1, PDX_JOIN_OUTER = 2, PDX_JOIN_SEMI = 3, PDX_JOIN_ANTI = 4 } pdx_join_how;
+typedef struct pdx_join pdx_join;
+int pdx_join_create(const pdx_column* left_key, const pdx_column* right_key, int how, void* stream, pdx_join** out);
+int pdx_join_rows(const pdx_join* j, int64_t* out_rows /* host */);
+int pdx_join_indices(pdx_join* j, pdx_mut_column* out_left, pdx_mut_column* out_right /* NULL for SEMI / ANTI */, void* stream);
+int pdx_join_last_plan(const pdx_join* j, char* buf, size_t buf_len);
+int pdx_join_destroy(pdx_join* j);
 
 /* ---------------------------------------------------------------- exact multi-GPU fp64 sum (partial-tree exchange)
  * The reference's per-group sum is Arrow's pairwise tree over the group's rows in GLOBAL row order; with row-range shards a

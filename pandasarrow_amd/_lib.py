@@ -36,6 +36,7 @@ ROUND_FLOOR, ROUND_CEIL, ROUND_NEAREST = range(3)  # pdx_round_mode
 (TC_YEAR, TC_MONTH, TC_DAY, TC_DAY_OF_WEEK, TC_DAY_OF_YEAR, TC_HOUR, TC_MINUTE, TC_SECOND, TC_MILLISECOND, TC_MICROSECOND, TC_NANOSECOND,
  TC_QUARTER, TC_ISO_WEEK, TC_ISO_YEAR, TC_ISO_DAY_OF_WEEK, TC_US_WEEK, TC_US_YEAR, TC_WEEK, TC_IS_LEAP_YEAR, TC_SUBSECOND) = range(20)  # pdx_temporal_component
 SORT_MAX_KEYS = 16  # PDX_SORT_MAX_KEYS
+JOIN_INNER, JOIN_LEFT, JOIN_OUTER, JOIN_SEMI, JOIN_ANTI = range(5)  # pdx_join_how
 ORIGIN_SHARD = 0x100  # OR-ed into the origin type for a row-range shard of a longer axis (include/pdx/abi.h)
 
 
@@ -148,6 +149,11 @@ ABI_SYMBOLS = {
     "pdx_index": (C.c_int, [_COL, C.POINTER(PdxScalar), C.POINTER(C.c_int64), _P]),
     "pdx_arg_extreme": (C.c_int, [C.c_int, _COL, C.c_int, C.POINTER(C.c_int64), _P]),
     "pdx_dictionary_encode": (C.c_int, [_COL, _MUT, _MUT, _P]),
+    "pdx_join_create": (C.c_int, [_COL, _COL, C.c_int, _P, C.POINTER(_P)]),
+    "pdx_join_rows": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "pdx_join_indices": (C.c_int, [_P, _MUT, _MUT, _P]),
+    "pdx_join_last_plan": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
+    "pdx_join_destroy": (C.c_int, [_P]),
     "pdx_groupby_group_values": (C.c_int, [_P, _COL, _P, C.POINTER(_P)]),
     "pdx_grouped_destroy": (C.c_int, [_P]),
     "pdx_grouped_counts": (C.c_int, [_P, _P, _P]),

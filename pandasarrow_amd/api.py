@@ -984,6 +984,77 @@ class DataFrame:
 
     reindexAsync = reindex
 
+    # ---- merge / join (the reference's README lists them; it has no implementation): pdx_join_create / pdx_join_indices, then pdx_take
+    def _join_plan(self, lkey: Column, rkey: Column, how):
+        """-> (left take indices, right take indices | None) of `how`; "right" is a left join with the sides swapped"""
+        if how not in ("inner", "left", "right", "outer", "semi", "anti"):
+            raise L.PdxError(L.INVALID, f"how is one of inner | left | right | outer | semi | anti, not {how!r}")
+        if how == "right":
+            ri, li = K.join_indices(rkey, lkey, "left")
+            return li, ri
+        return K.join_indices(lkey, rkey, how)
+
+    def merge(self, right: "DataFrame", on=None, left_on=None, right_on=None, how="inner", suffixes=("_x", "_y")):
+        """Database-style join of two frames on one key column each (int64, uint64, timestamp[ns] or int32, the same dtype on both sides).
+        Rows: ordered by left row, the matches of a left row by ascending right row; "left" keeps a left row without a match (null right
+        cells), "outer" appends the right rows no left row matched, "right" is "left" with the sides swapped, "semi" / "anti" give the left
+        rows with / without a match and the left columns only.  A NULL KEY MATCHES NOTHING (Arrow's hash join and SQL; pandas differs).
+        With `on` (or equal left_on / right_on) the key column appears once -- for "outer" coalesce(left key, right key); other columns
+        both frames name take the suffixes.  The result has the default range index."""
+        if on is not None:
+            if left_on is not None or right_on is not None:
+                raise L.PdxError(L.INVALID, "merge: pass either `on` or `left_on` and `right_on`")
+            left_on = right_on = on
+        if left_on is None or right_on is None:
+            raise L.PdxError(L.INVALID, "merge: a key is required (`on`, or `left_on` and `right_on`)")
+        for frame, key in ((self, left_on), (right, right_on)):
+            if key not in frame.names:
+                raise L.PdxError(L.INVALID, f"{key} not in schema")
+        lkey, rkey = self.cols[self.names.index(left_on)], right.cols[right.names.index(right_on)]
+        li, ri = self._join_plan(lkey, rkey, how)
+        lcols = _take_all(self.cols, li)
+        if ri is None:  # semi / anti: the left rows alone
+            return DataFrame(dict(zip(self.names, lcols)))
+        rcols = _take_all(right.cols, ri)
+        shared_key = left_on == right_on
+        if shared_key:
+            at = self.names.index(left_on)
+            rkey_taken = rcols[right.names.index(right_on)]
+            if how == "outer":
+                lcols[at] = K.coalesce([lcols[at], rkey_taken])
+            elif how == "right":
+                lcols[at] = rkey_taken
+        out = {}
+        rnames = [nm for nm in right.names if not (shared_key and nm == right_on)]
+        for nm, c in zip(self.names, lcols):
+            out[nm + suffixes[0] if nm in rnames else nm] = c
+        for nm, c in zip(right.names, rcols):
+            if shared_key and nm == right_on:
+                continue
+            clash = nm in self.names
+            name = nm + suffixes[1] if clash else nm
+            if name in out:
+                raise L.PdxError(L.INVALID, f"merge: the suffixes {suffixes!r} leave two columns named {name!r}")
+            out[name] = c
+        if len(out) != len(lcols) + len(rnames):
+            raise L.PdxError(L.INVALID, f"merge: the suffixes {suffixes!r} leave two columns of one name")
+        return DataFrame(out)
+
+    def join(self, other: "DataFrame", how="left"):
+        """Join on the index labels (int64, uint64, timestamp[ns] or int32 of one dtype; a frame without an index joins on its row numbers):
+        the rows of merge on the two indexes, the result's index = coalesce(left labels, right labels).  Column names must be distinct."""
+        both = [nm for nm in self.names if nm in other.names]
+        if both and how not in ("semi", "anti"):
+            raise L.PdxError(L.INVALID, f"join: columns overlap but no suffix is given: {both}")
+        lix, rix = _join_labels(self, other), _join_labels(other, self)
+        li, ri = self._join_plan(lix, rix, how)
+        louts = _take_all(self.cols + [lix], li)
+        if ri is None:
+            return DataFrame(dict(zip(self.names, louts[:-1])), index=louts[-1])
+        routs = _take_all(other.cols + [rix], ri)
+        index = louts[-1] if how in ("inner", "left") else routs[-1] if how == "right" else K.coalesce([louts[-1], routs[-1]])
+        return DataFrame(dict(zip(self.names + other.names, louts[:-1] + routs[:-1])), index=index)
+
     # ---- Arrow IPC (src/dataframe.cpp:726-791)
     def toBinary(self, columns=None, index=None, metadata=None) -> bytes:
         """DataFrame::toBinary: one IPC stream (schema + ONE record batch + custom metadata).  Like the reference, every column
@@ -1382,6 +1453,24 @@ def _label_bits(c: Column) -> Column:
 
 def _frame_index(f):
     return f.index if f.index is not None else Column(L.UINT64, f.num_rows(), torch.arange(max(f.num_rows(), 1), dtype=torch.int64, device=K._device()), None)
+
+
+def _take_all(cols, idx: Column):
+    """pdx_take of any number of columns (it serves 16 a call)"""
+    outs = []
+    for at in range(0, len(cols), 16):
+        outs += K.take(cols[at:at + 16], idx)
+    return outs
+
+
+def _join_labels(f, other):
+    """the labels DataFrame.join matches: the index; for a frame without one its row numbers, in the other frame's 8-byte label dtype"""
+    if f.index is not None:
+        return f.index
+    ix = _frame_index(f)
+    if other.index is not None and other.index.dtype in (L.INT64, L.TIMESTAMP_NS):
+        ix = Column(other.index.dtype, ix.length, ix.values, None)
+    return ix
 
 
 def _same_labels(a: Column, b: Column):

@@ -506,6 +506,70 @@ def dictionary_encode(a: Column):
     return codes._adopt(mc), dic._adopt(md)
 
 
+# ---------------------------------------------------------------- join
+JOIN_HOW = {"inner": L.JOIN_INNER, "left": L.JOIN_LEFT, "outer": L.JOIN_OUTER, "semi": L.JOIN_SEMI, "anti": L.JOIN_ANTI}
+
+
+class JoinHandle:
+    """Owner of a pdx_join*: the matched key columns of two frames.  ``rows`` is the size of the result; ``indices()`` writes it as INT64
+    take indices into the left and the right frame (include/pdx/abi.h, "join")."""
+
+    def __init__(self, left_key: Column, right_key: Column, how):
+        self.how = JOIN_HOW[how] if isinstance(how, str) else int(how)
+        self._h = C.c_void_p()
+        cl, cr = left_key.c(), right_key.c()
+        L.check(L.load().pdx_join_create(C.byref(cl), C.byref(cr), self.how, _stream(), C.byref(self._h)))
+        n = C.c_int64(0)
+        L.check(L.load().pdx_join_rows(self._h, C.byref(n)))
+        self.rows = int(n.value)
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            L.load().pdx_join_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def has_right(self):
+        return self.how not in (L.JOIN_SEMI, L.JOIN_ANTI)
+
+    def indices(self, out_left=None, out_right=None):
+        """-> (left indices, right indices | None).  Without arguments the outputs are allocated at exactly ``rows`` rows, with the
+        validity buffers the join kind requires; a caller's own columns are written in place (their length is the capacity)."""
+        if out_left is None:
+            out_left = Column.empty(L.INT64, self.rows, with_validity=self.how == L.JOIN_OUTER)
+        if out_right is None and self.has_right:
+            out_right = Column.empty(L.INT64, self.rows, with_validity=self.how != L.JOIN_INNER)
+        ml = out_left.mut()
+        mr = out_right.mut() if out_right is not None else None
+        L.check(L.load().pdx_join_indices(self._h, C.byref(ml), None if mr is None else C.byref(mr), _stream()))
+        out_left._adopt(ml)
+        if out_right is not None:
+            out_right._adopt(mr)
+        return out_left, out_right
+
+    def plan(self) -> dict:
+        """{'plan': 'lds' | 'global' | 'empty', 'build_rows': ..., 'distinct': ..., 'out_rows': ...} (pdx_join_last_plan)"""
+        buf = C.create_string_buffer(256)
+        L.check(L.load().pdx_join_last_plan(self._h, buf, 256))
+        return dict(w.split("=", 1) for w in buf.value.decode().split() if "=" in w)
+
+
+def join_indices(left_key: Column, right_key: Column, how="inner"):
+    """The take indices of `left_key` JOIN `right_key` -> (left indices, right indices | None for semi / anti) (pdx_join_create +
+    pdx_join_indices).  A null key matches nothing; the row order is defined by include/pdx/abi.h."""
+    h = JoinHandle(left_key, right_key, how)
+    try:
+        return h.indices()
+    finally:
+        h.close()
+
+
 # ---------------------------------------------------------------- filter / take / concat
 def _col_array(cols):
     arr = (L.PdxColumn * len(cols))(*[c.c() for c in cols])

@@ -1293,6 +1293,71 @@ class DataFrame {
     auto outs = Series::run_take(columns_with_index(), idx.m_array);
     return rebuild(outs);
   }
+  // ---- merge / join.  The reference's README lists "merging and joining" and implements neither; these follow pandas' signatures over
+  // pdx_join_create / pdx_join_indices (pdx/abi.h, "join") and pdx_take.  One key column per side: int64, uint64, timestamp[ns] or int32,
+  // the same dtype on both sides.  Row order: by left row, the matches of one left row by ascending right row; "left" keeps a left row
+  // without a match (null right cells), "outer" appends the right rows that no left row matched, "right" is "left" with the sides swapped,
+  // "semi" / "anti" return the left rows with / without a match and the left columns only.  A NULL KEY MATCHES NOTHING (Arrow's hash join
+  // and SQL; pandas matches nulls with each other).  With one key name on both sides the key column appears once -- for "outer"
+  // coalesce(left key, right key) -- and other columns that both frames name take the suffixes.  The result has the default range index.
+  DataFrame merge(const DataFrame& right, const std::string& on, const std::string& how = "inner",
+                  std::pair<std::string, std::string> suffixes = {"_x", "_y"}) const {
+    return merge(right, on, on, how, suffixes);
+  }
+  DataFrame merge(const DataFrame& right, const std::string& left_on, const std::string& right_on, const std::string& how,
+                  std::pair<std::string, std::string> suffixes = {"_x", "_y"}) const {
+    const size_t lk = (size_t)column_index(left_on), rk = (size_t)right.column_index(right_on);
+    const JoinIndices ix = join_plan(m_columns[lk], right.m_columns[rk], how);
+    std::vector<Array> lcols = take_all(m_columns, ix.left);
+    if (!ix.right) return DataFrame(m_names, lcols);
+    std::vector<Array> rcols = take_all(right.m_columns, *ix.right);
+    const bool shared_key = left_on == right_on;
+    if (shared_key && how == "outer") lcols[lk] = DataFrame({"l", "r"}, {lcols[lk], rcols[rk]}).coalesce().m_array;
+    if (shared_key && how == "right") lcols[lk] = rcols[rk];
+    auto named_by = [](const DataFrame& f, const std::string& nm) { return std::find(f.m_names.begin(), f.m_names.end(), nm) != f.m_names.end(); };
+    std::vector<std::string> names;
+    std::vector<Array> cols;
+    for (size_t i = 0; i < m_names.size(); ++i) {
+      const bool clash = named_by(right, m_names[i]) && !(shared_key && m_names[i] == left_on);
+      names.push_back(clash ? m_names[i] + suffixes.first : m_names[i]);
+      cols.push_back(lcols[i]);
+    }
+    for (size_t i = 0; i < right.m_names.size(); ++i) {
+      if (shared_key && i == rk) continue;
+      names.push_back(named_by(*this, right.m_names[i]) ? right.m_names[i] + suffixes.second : right.m_names[i]);
+      cols.push_back(rcols[i]);
+    }
+    for (size_t i = 0; i < names.size(); ++i)
+      if (std::count(names.begin(), names.end(), names[i]) > 1) throw std::runtime_error("merge: the suffixes leave two columns named " + names[i]);
+    return DataFrame(names, cols);
+  }
+  // join on the index labels (the dtypes of merge's keys; a frame without an index joins on its row numbers): the rows of merge over the
+  // two indexes, the result's index = coalesce(left labels, right labels).  Column names must be distinct.
+  DataFrame join(const DataFrame& other, const std::string& how = "left") const {
+    if (how != "semi" && how != "anti")
+      for (auto& nm : m_names)
+        if (std::find(other.m_names.begin(), other.m_names.end(), nm) != other.m_names.end())
+          throw std::runtime_error("join: columns overlap but no suffix is given: " + nm);
+    const Array lix = join_labels(other), rix = other.join_labels(*this);
+    const JoinIndices ix = join_plan(lix, rix, how);
+    std::vector<Array> lin = m_columns;
+    lin.push_back(lix);
+    std::vector<Array> louts = take_all(lin, ix.left);
+    Array index = louts.back();
+    louts.pop_back();
+    if (!ix.right) return DataFrame(m_names, louts, index);
+    std::vector<Array> rin = other.m_columns;
+    rin.push_back(rix);
+    std::vector<Array> routs = take_all(rin, *ix.right);
+    if (how == "right") index = routs.back();
+    if (how == "outer") index = DataFrame({"l", "r"}, {index, routs.back()}).coalesce().m_array;
+    routs.pop_back();
+    std::vector<std::string> names = m_names;
+    names.insert(names.end(), other.m_names.begin(), other.m_names.end());
+    louts.insert(louts.end(), routs.begin(), routs.end());
+    return DataFrame(names, louts, index);
+  }
+
   // DataFrame::sort_index (src/dataframe.cpp:1062-1071): the index sorted (array_sort_indices), the frame taken by the same indices.
   // Also the order-independent view of a group-by result: group ORDER is first occurrence here and a bounded permutation of it in
   // Arrow's Grouper (pdx/abi.h at pdx_groupby_create); sorted by key both frames are identical.
@@ -1477,6 +1542,61 @@ class DataFrame {
   void check() const {
     for (auto& c : m_columns)
       if (c.length != num_rows()) throw std::runtime_error("all columns must have the same length");
+  }
+  struct JoinIndices {  // INT64 take indices into the left / the right frame (no right ones for semi / anti)
+    Array left;
+    std::optional<Array> right;
+  };
+  static JoinIndices run_join(const Array& lkey, const Array& rkey, int how) {
+    auto cl = lkey.c(), cr = rkey.c();
+    pdx_join* h = nullptr;
+    ThrowOnFailure(pdx_join_create(&cl, &cr, how, nullptr, &h));
+    struct Closer {
+      pdx_join* h;
+      ~Closer() { pdx_join_destroy(h); }
+    } closer{h};
+    int64_t rows = 0;
+    ThrowOnFailure(pdx_join_rows(h, &rows));
+    const bool has_right = how != PDX_JOIN_SEMI && how != PDX_JOIN_ANTI;
+    JoinIndices out;
+    out.left = Array::Empty(PDX_INT64, rows, how == PDX_JOIN_OUTER);
+    auto ml = out.left.mut();
+    pdx_mut_column mr{};
+    if (has_right) {
+      out.right = Array::Empty(PDX_INT64, rows, how != PDX_JOIN_INNER);
+      mr = out.right->mut();
+    }
+    ThrowOnFailure(pdx_join_indices(h, &ml, has_right ? &mr : nullptr, nullptr));
+    out.left.null_count = ml.null_count;
+    if (has_right) out.right->null_count = mr.null_count;
+    return out;
+  }
+  static JoinIndices join_plan(const Array& lkey, const Array& rkey, const std::string& how) {
+    if (how == "right") {  // a left join with the sides swapped
+      JoinIndices sw = run_join(rkey, lkey, PDX_JOIN_LEFT);
+      return JoinIndices{*sw.right, sw.left};
+    }
+    static const std::map<std::string, int> kinds = {{"inner", PDX_JOIN_INNER}, {"left", PDX_JOIN_LEFT}, {"outer", PDX_JOIN_OUTER}, {"semi", PDX_JOIN_SEMI}, {"anti", PDX_JOIN_ANTI}};
+    auto it = kinds.find(how);
+    if (it == kinds.end()) throw std::runtime_error("how is one of inner | left | right | outer | semi | anti, not " + how);
+    return run_join(lkey, rkey, it->second);
+  }
+  static std::vector<Array> take_all(const std::vector<Array>& cols, const Array& idx) {  // (pdx_take serves 16 columns per call)
+    std::vector<Array> outs;
+    for (size_t at = 0; at < cols.size(); at += 16) {
+      std::vector<Array> part(cols.begin() + (std::ptrdiff_t)at, cols.begin() + (std::ptrdiff_t)std::min(cols.size(), at + 16));
+      for (auto& a : Series::run_take(part, idx)) outs.push_back(a);
+    }
+    return outs;
+  }
+  // the labels join() matches: the index; for a frame without one its row numbers, in the other frame's 8-byte label dtype where it has one
+  Array join_labels(const DataFrame& other) const {
+    if (m_index) return *m_index;
+    std::vector<int64_t> r((size_t)num_rows());
+    for (size_t i = 0; i < r.size(); ++i) r[i] = (int64_t)i;
+    Array a = Array::Make(r);
+    if (other.m_index && (other.m_index->dtype == PDX_UINT64 || other.m_index->dtype == PDX_TIMESTAMP_NS)) a.dtype = other.m_index->dtype;
+    return a;
   }
   std::vector<Array> columns_with_index() const {
     std::vector<Array> cols = m_columns;

@@ -19,14 +19,11 @@
 #include <algorithm>
 #include <vector>
 #include "colview.hpp"
+#include "lookup_table.hpp"
 
 namespace pdx {
 
-constexpr int kLkBlock = 256;
-constexpr int kLkWaves = kLkBlock / 64;
-constexpr int64_t kLkLdsMaxEntries = 2048;  // 4096 slots * (8 + 4) B = 48 KB of LDS per workgroup
-constexpr uint32_t kLkEmpty = 0xFFFFFFFFu;  // a slot without a value (positions are < 2^31 - 1)
-
+// (the table itself -- constants, k_lk_insert, k_lk_keys, k_lk_widen -- lives in lookup_table.hpp, shared with join.hip)
 static thread_local std::string g_lookup_plan = "plan=empty set_size=0 slots=0";
 
 template <typename U>
@@ -46,54 +43,12 @@ __device__ __forceinline__ void lk_load2(const U* __restrict__ p, int64_t i, int
     *x1 = i + 1 < n ? p[i + 1] : U(0);
   }
 }
-// bits 0..31 of x moved to the even bit positions of a 64-bit word (wave-uniform operands: scalar instructions)
-__device__ __forceinline__ uint64_t lk_spread(uint64_t x) {
-  x &= 0xFFFFFFFFull;
-  x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-  x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-  x = (x | (x << 2)) & 0x3333333333333333ull;
-  x = (x | (x << 1)) & 0x5555555555555555ull;
-  return x;
-}
 // the validity of the 64 rows from row i0 + 64 * w of a tile (bits of rows >= n are clear); all operands wave-uniform
 __device__ __forceinline__ uint64_t lk_valid_word(const uint8_t* valid, int64_t voff, int64_t i0, int64_t n, int w) {
   const int64_t rem = n - i0 - 64 * (int64_t)w;
   if (rem <= 0) return 0ull;
   const uint64_t in = in_range_mask(rem);
   return valid ? (load_bits64_uniform(valid, voff + i0 + 64 * (int64_t)w, (int)(rem < 64 ? rem : 64)) & in) : in;
-}
-
-// ---------------------------------------------------------------- build
-template <typename U>
-__global__ void __launch_bounds__(256) k_lk_insert(const U* __restrict__ set, const uint8_t* __restrict__ valid, int64_t voff, int64_t m, uint32_t* __restrict__ pos,
-                                                   uint32_t mask, uint32_t* __restrict__ first_null) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) {
-    if (valid && !bit_get(valid, voff + j)) {
-      atomicMin(first_null, (uint32_t)j);
-      continue;
-    }
-    const U k = set[j];
-    uint32_t h = (uint32_t)splitmix64((uint64_t)k) & mask;
-    for (uint64_t step = 0; step <= (uint64_t)mask; ++step) {  // (an empty slot exists: at most half of them are taken)
-      const uint32_t p = atomicCAS(&pos[h], kLkEmpty, (uint32_t)j);
-      if (p == kLkEmpty) break;
-      if (set[p] == k) {  // (p < m: only positions are ever stored)
-        atomicMin(&pos[h], (uint32_t)j);
-        break;
-      }
-      h = (h + 1) & mask;
-    }
-  }
-}
-template <typename U>
-__global__ void __launch_bounds__(256) k_lk_keys(const U* __restrict__ set, const uint32_t* __restrict__ pos, uint64_t slots, U* __restrict__ keys) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < slots; h += stride) {
-    const uint32_t p = pos[h];
-    keys[h] = p == kLkEmpty ? U(0) : set[p];
-  }
 }
 
 // ---------------------------------------------------------------- probe
@@ -332,11 +287,6 @@ __global__ void __launch_bounds__(64) k_ax_final(const AxPair* __restrict__ part
 }
 
 // ---------------------------------------------------------------- dictionary_encode (over the group-by handle)
-// a 4-byte column as the 8-byte key the group-by takes: the bit image, zero-extended
-__global__ void k_lk_widen(const uint32_t* __restrict__ v, int64_t n, unsigned long long* __restrict__ out) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (unsigned long long)v[i];
-}
 // ctl[1] = the id of the null key's group (it stays ~0 without one)
 __global__ void k_lk_null_group(const uint8_t* __restrict__ uvalid, int64_t G, unsigned long long* __restrict__ ctl) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -374,15 +324,6 @@ __global__ void k_lk_dict(const unsigned long long* __restrict__ uniq, int64_t G
 }
 
 // ---------------------------------------------------------------- host
-static int64_t lookup_lds_max() {
-  int64_t lim = kLkLdsMaxEntries;
-  if (const char* e = getenv("PDX_LOOKUP_LDS_MAX")) {
-    char* end = nullptr;
-    const long long x = strtoll(e, &end, 10);
-    if (end != e) lim = std::min<int64_t>(kLkLdsMaxEntries, std::max<long long>(0, x));  // (never above what the LDS holds)
-  }
-  return lim;
-}
 static bool lookup_dtype(int dt) { return is_int_like(dt) || dt == PDX_FLOAT64 || is_narrow(dt); }
 
 template <typename U, bool INDEX>

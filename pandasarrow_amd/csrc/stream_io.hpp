@@ -20,10 +20,11 @@ enum StreamId : unsigned {
   kStreamHistKeys = 4,    // e: loads of k_radix_hist
   kStreamFlrTile = 5,     // f: key and value loads of k_flr_reduce's load_tile
   kStreamScatOut = 6,     // g: the scatter's output stores
+  kStreamJoinOut = 7,     // h: the two index columns k_join_expand writes
 };
 #ifndef PDX_STREAM_NT
-//                      gfedcba
-#define PDX_STREAM_NT 0b0011001
+//                      hgfedcba
+#define PDX_STREAM_NT 0b10011001
 #endif
 constexpr unsigned kStreamNtMask = PDX_STREAM_NT;
 constexpr bool stream_nt(StreamId s) { return (kStreamNtMask >> (unsigned)s) & 1u; }

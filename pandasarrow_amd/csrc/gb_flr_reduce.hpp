@@ -18,6 +18,18 @@ constexpr int kFlrLevels = 20;  // a group lies inside one run, a run is <= 2^19
 #ifndef PDX_FLR_DENSE_WAVES
 #define PDX_FLR_DENSE_WAVES 1
 #endif
+#ifndef PDX_FLR_BATCH_RANK
+#define PDX_FLR_BATCH_RANK 1
+#endif
+#ifndef PDX_FLR_DPP_SCAN
+#define PDX_FLR_DPP_SCAN 1
+#endif
+constexpr bool kFlrDppScan = PDX_FLR_DPP_SCAN != 0;      // dense instantiation: the per-tile digit prefix by DPP instead of LDS shuffles
+#ifndef PDX_FLR_RANK_GROUP
+#define PDX_FLR_RANK_GROUP 2
+#endif
+constexpr int kFlrRankGroup = PDX_FLR_RANK_GROUP;        // steps whose match words the batched ranking holds in registers at a time
+constexpr bool kFlrBatchRank = PDX_FLR_BATCH_RANK != 0;  // dense instantiation: all steps of a tile ranked in one LDS exchange (wave_match_rank_batch)
 constexpr int kFlrDenseWaves = PDX_FLR_DENSE_WAVES;  // diagnostic: minimum waves per SIMD the dense instantiation is compiled for
 constexpr int kFlrItems = PDX_FLR_ITEMS;   // rows per thread and tile: 3072-row tiles (measured best: 4096 -> 5.6 ms, 3072 -> 4.2 ms, 2048 -> 4.5 ms per 1e9 rows)
 constexpr int kFlrTile = kSortBlock * kFlrItems;
@@ -180,6 +192,64 @@ __device__ __forceinline__ void flr_counter_push(double (*csum)[1 << kFlrBits], 
 }  // namespace pdx
 #include "flr_wave.hpp"
 namespace pdx {
+// wave_match_rank for all ITEMS steps of a wave's tile at once: the ORs of every step are issued back to back, so the wave waits for
+// the LDS round trip of the exchange once per tile instead of three times per step (the form flr_wave.hpp uses).  Ranks and counters
+// are the same.  M: the wave's own [ITEMS][64] 64-bit words, any content on entry, dead on exit; cnt: the wave's [64] counters, any
+// content on entry, on exit the wave's rows per digit (what ITEMS calls of wave_match_rank leave in zeroed counters).  Row q * 64 + lane
+// of the wave is active when it lies below rows_wave.  All lanes of the wave must be here.  Everything is ordered by the wave's own
+// in-order LDS queue (the fact wave_match_rank relies on); the wavefront fences only keep the compiler from moving an access across
+// a phase.
+//   1  lane l zeroes M[q][l]                                    (consecutive addresses)
+//   2  every active row ORs its lane bit into M[q][digit]
+//   3  every row reads its word back (rank inside its step = peers in lower lanes), and lane l, as owner of digit l, reads M[q][l]:
+//      its running sum of their popcounts over q is the digit's rows in front of step q
+//   4  every row fetches that sum from its digit's owner lane (one shuffle per step); the owner's total goes to cnt[l]
+// Phases 3 and 4 go GROUP steps at a time: all ITEMS at once keep 4 * ITEMS registers in flight and cost the kernel its third workgroup
+// per CU, and measured no faster.  (Writing the sums back into the words and reading them with the row's digit, as phase 3
+// does -- no shuffle, two more LDS round trips per tile -- was 0.04 ms per 1e9 rows slower.)
+template <int ITEMS, int GROUP>
+__device__ __forceinline__ void wave_match_rank_batch(unsigned long long* M, uint32_t* cnt, const uint32_t (&d)[ITEMS], int rows_wave, int lane, uint64_t lt_mask,
+                                                      uint32_t (&rank)[ITEMS]) {
+#pragma unroll
+  for (int q = 0; q < ITEMS; ++q) __hip_atomic_store(&M[q * 64 + lane], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+  for (int q = 0; q < ITEMS; ++q)
+    if (q * 64 + lane < rows_wave) __hip_atomic_fetch_or(&M[q * 64 + d[q]], 1ull << lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  uint32_t tot = 0;
+#pragma unroll
+  for (int q0 = 0; q0 < ITEMS; q0 += GROUP) {
+    unsigned long long peers[GROUP], own[GROUP];
+#pragma unroll
+    for (int g = 0; g < GROUP; ++g)
+      if (q0 + g < ITEMS) peers[g] = __hip_atomic_load(&M[(q0 + g) * 64 + d[q0 + g]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#pragma unroll
+    for (int g = 0; g < GROUP; ++g)
+      if (q0 + g < ITEMS) own[g] = __hip_atomic_load(&M[(q0 + g) * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#pragma unroll
+    for (int g = 0; g < GROUP; ++g)
+      if (q0 + g < ITEMS) {
+        rank[q0 + g] = (uint32_t)__popcll(peers[g] & lt_mask) + (uint32_t)__shfl((int)tot, (int)d[q0 + g], 64);
+        tot += (uint32_t)__popcll(own[g]);
+      }
+  }
+  __hip_atomic_store(&cnt[lane], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+// Inclusive sum over the 64 lanes of a wave (all of them active) in the vector ALU: four row_shr steps inside every row of 16 lanes, then
+// row_bcast:15 hands every row's total to the next row (rows 1 and 3 take it) and row_bcast:31 the total of rows 0-1 to rows 2-3.
+// wave_inclusive_scan does the same with six dependent __shfl_up, each a trip through the LDS crossbar -- on the per-tile prefix of
+// k_flr_reduce that is time all four waves of the workgroup wait for.  Lanes without a source add the 0 passed as the old value.
+__device__ __forceinline__ uint32_t wave_inclusive_sum_dpp(uint32_t x) {
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);   // row_shr:1
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);   // row_shr:2
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);   // row_shr:4
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);   // row_shr:8
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
+  return x;
+}
 // Segmented "run of valid rows" state of a chunk of staged rows, packed in 32 bits, for the nullable leaf phase: bits 0-11 valid rows at
 // the chunk's end since its last break, bit 12 the chunk holds a break (a null row or a group boundary), bits 13-14 the kind of its
 // last break (1 null, 2 group boundary), bits 16-22 group boundaries in the chunk.  Associative, earlier operand first.
@@ -212,7 +282,17 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
   __shared__ __attribute__((aligned(16))) T svals[DENSE_PW ? 16 * kFlrLeafStride : kFlrTile + R];
   __shared__ __attribute__((aligned(8))) uint8_t snull[kFlrTile + R];
   __shared__ uint32_t cnt[kSortWaves][R];
-  __shared__ unsigned long long match[kSortWaves][R];  // match-any words of the ranking (wave_match_rank)
+  // Dense instantiation: the ranking's words live in svals (20 KB of its 35 KB), M[wave][step][digit], 64-bit.  svals is staged into
+  // after the prefix barrier of a tile and read by the leaf sums, which end at the tile's last barrier; from there to the next tile's
+  // staging nobody touches it -- wave 0's pushes read leafsum (in snull) and csum only.  So a wave may start on its words
+  //   waves 1-3: after the barrier that ends the previous tile's leaf sums,
+  //   wave 0:    after its pushes (it reaches the ranking only then),
+  //   the first tile of a run: after the __syncthreads() that ends the previous run (or the kernel's first one),
+  // which is where the ranking stands in program order; the words are dead again before the ranking barrier, two barriers ahead of
+  // the staging.  The other instantiations let wave 0 read svals after a tile's last barrier: they keep wave_match_rank and its array.
+  constexpr bool kBatch = DENSE_PW && kFlrBatchRank;
+  static_assert(!kBatch || sizeof(T) * 16 * kFlrLeafStride >= sizeof(unsigned long long) * kSortWaves * kFlrItems * R, "the match words alias the value staging area");
+  __shared__ unsigned long long match[kBatch ? 1 : kSortWaves][kBatch ? 1 : R];  // match-any words of the ranking (wave_match_rank)
   __shared__ uint32_t dstart[R + 1];
   constexpr int kLevels = DENSE_PW ? kFlrDenseLevels : kFlrLevels;
   __shared__ double csum[kLevels][R];
@@ -236,7 +316,7 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
   // staging lies behind two barriers that wave 0 itself has to reach.
   for (int d = tid; d < kSortWaves * R; d += kSortBlock) {
     (&cnt[0][0])[d] = 0;
-    (&match[0][0])[d] = 0;
+    if constexpr (!kBatch) (&match[0][0])[d] = 0;
   }
   __syncthreads();
 #ifdef PDX_FLR_TIMING
@@ -284,12 +364,20 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
       const int rows = (int)(e - t0 < kFlrTile ? e - t0 : kFlrTile);
       uint32_t rank[kFlrItems];
       FLR_T(0);  // wave 0: the previous tile's pushes; others: nothing
+      if constexpr (kBatch) {
+        // (from here on key[] holds the digits: this path has no null flags to keep)
 #pragma unroll
-      for (int q = 0; q < kFlrItems; ++q) {
-        const int r = wave * (64 * kFlrItems) + q * 64 + lane;
-        const bool active = r < rows;
-        const uint32_t d = sizeof(KT) == 4 ? ((key[q] & kSortKeyMask) >> low_bits) & (R - 1) : key[q] & (R - 1);
-        rank[q] = wave_match_rank(match[wave], cnt[wave], d, active, lane, lt_mask);
+        for (int q = 0; q < kFlrItems; ++q) key[q] = sizeof(KT) == 4 ? ((key[q] & kSortKeyMask) >> low_bits) & (R - 1) : key[q] & (R - 1);
+        wave_match_rank_batch<kFlrItems, kFlrRankGroup>(reinterpret_cast<unsigned long long*>(svals) + wave * (kFlrItems * R), cnt[wave], key, rows - wave * (64 * kFlrItems), lane,
+                                                        lt_mask, rank);
+      } else {
+#pragma unroll
+        for (int q = 0; q < kFlrItems; ++q) {
+          const int r = wave * (64 * kFlrItems) + q * 64 + lane;
+          const bool active = r < rows;
+          const uint32_t d = sizeof(KT) == 4 ? ((key[q] & kSortKeyMask) >> low_bits) & (R - 1) : key[q] & (R - 1);
+          rank[q] = wave_match_rank(match[wave], cnt[wave], d, active, lane, lt_mask);
+        }
       }
       FLR_T(1);  // ranking (includes waiting for this tile's loads)
       __syncthreads();
@@ -313,7 +401,7 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
           // leaves are scanned in one word (<= 2560 rows, <= 280 leaves)
           const int c = (int)tot;
           const uint32_t nl = c > 0 ? (uint32_t)(pos + c + 15) >> 4 : 0u;
-          const uint32_t both = wave_inclusive_scan(tot | (nl << 16), SumOp());
+          const uint32_t both = kFlrDppScan ? wave_inclusive_sum_dpp(tot | (nl << 16)) : wave_inclusive_scan(tot | (nl << 16), SumOp());
           inc = both & 0xFFFFu;
           ex = inc - tot;
           const uint32_t lincl = both >> 16, lex = lincl - nl;
@@ -358,14 +446,14 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
       // (all bases are requested before the first staged write: reads behind a byte store would wait for it)
 #pragma unroll
       for (int q = 0; q < kFlrItems; ++q) {
-        const uint32_t d = sizeof(KT) == 4 ? ((key[q] & kSortKeyMask) >> low_bits) & (R - 1) : key[q] & (R - 1);
+        const uint32_t d = kBatch ? key[q] : sizeof(KT) == 4 ? ((key[q] & kSortKeyMask) >> low_bits) & (R - 1) : key[q] & (R - 1);
         rank[q] += cnt[wave][d];
       }
 #pragma unroll
       for (int q = 0; q < kFlrItems; ++q) {
         const int r = wave * (64 * kFlrItems) + q * 64 + lane;
         if (r < rows) {
-          const uint32_t d = sizeof(KT) == 4 ? ((key[q] & kSortKeyMask) >> low_bits) & (R - 1) : key[q] & (R - 1);
+          const uint32_t d = kBatch ? key[q] : sizeof(KT) == 4 ? ((key[q] & kSortKeyMask) >> low_bits) & (R - 1) : key[q] & (R - 1);
           uint32_t p = rank[q];
           if (dense_pw) {
             if ((p & 15u) == 0) leaf_d[p >> 4] = (uint8_t)d;  // this row opens a leaf
@@ -374,7 +462,7 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
             p += d;
           }
           svals[p] = val[q];
-          if (nullable) snull[p] = (uint8_t)(key[q] >> (8 * (int)sizeof(KT) - 1));
+          if (!DENSE_PW && nullable) snull[p] = (uint8_t)(key[q] >> (8 * (int)sizeof(KT) - 1));  // (the dense path is never launched on nullable values)
         }
       }
       FLR_T(5);  // staging
@@ -382,7 +470,8 @@ __global__ void __launch_bounds__(kSortBlock, (DENSE_PW ? kFlrDenseWaves : 1)) k
       FLR_T(9);  // issuing the next tile's loads
       __syncthreads();
       FLR_T(6);
-      for (int d = tid; d < kSortWaves * R; d += kSortBlock) (&cnt[0][0])[d] = 0;  // (free again: the bases were consumed above)
+      if constexpr (!kBatch)  // (the batched ranking overwrites its counters instead of adding to them)
+        for (int d = tid; d < kSortWaves * R; d += kSortBlock) (&cnt[0][0])[d] = 0;  // (free again: the bases were consumed above)
       if (dense_pw) {
         const int NL = lp[R];
         for (int Lf = tid; Lf < NL; Lf += kSortBlock) {

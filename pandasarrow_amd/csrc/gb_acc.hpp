@@ -552,33 +552,19 @@ static int reduce_acc(pdx_groupby* gb, const AccGeom& g, const pdx_column* value
     PDX_SCRATCH_CHECK(s);
     int rc = PDX_OK;
     if (need_vals) {
-#define ACC_P0(B)                                                                                                                                  \
-  rc = nullable ? radix_scatter_narrow<B, uint64_t, uint32_t, uint16_t, true>(gb->slot_of_row, vin, k16, nv, n, gb->pass0_off, st, vvalid, values->offset) \
-                : radix_scatter_narrow<B, uint64_t, uint32_t, uint16_t>(gb->slot_of_row, vin, k16, nv, n, gb->pass0_off, st)
-      switch (g.b0) {
-        case 4: ACC_P0(4); break;
-        case 5: ACC_P0(5); break;
-        case 6: ACC_P0(6); break;
-        case 7: ACC_P0(7); break;
-        default: ACC_P0(8); break;
-      }
-#undef ACC_P0
+      rc = with_digit_bits<4, 8>(g.b0, [&](auto b) {
+        return nullable ? radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t, true>(gb->slot_of_row, vin, k16, nv, n, gb->pass0_off, st, vvalid, values->offset)
+                        : radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t>(gb->slot_of_row, vin, k16, nv, n, gb->pass0_off, st);
+      });
       desc += " sort=part:" + std::to_string(g.b0);
     } else {
       PDX_PROFILE("acc_partition_keys", st);
       const unsigned ntiles = (unsigned)ceil_div(n, kSortTile);
       const int swz = sort_xcd_swizzle();
-#define ACC_PK(B)                                                                                                                                     \
-  if (nullable) hipLaunchKernelGGL((k_acc_part_keys<B, true>), dim3(ntiles), dim3(kSortBlock), 0, st, gb->slot_of_row, vvalid, values->offset, n, gb->pass0_off, k16, swz); \
-  else hipLaunchKernelGGL((k_acc_part_keys<B, false>), dim3(ntiles), dim3(kSortBlock), 0, st, gb->slot_of_row, vvalid, values->offset, n, gb->pass0_off, k16, swz)
-      switch (g.b0) {
-        case 4: ACC_PK(4); break;
-        case 5: ACC_PK(5); break;
-        case 6: ACC_PK(6); break;
-        case 7: ACC_PK(7); break;
-        default: ACC_PK(8); break;
-      }
-#undef ACC_PK
+      with_digit_bits<4, 8>(g.b0, [&](auto b) {
+        if (nullable) hipLaunchKernelGGL((k_acc_part_keys<b(), true>), dim3(ntiles), dim3(kSortBlock), 0, st, gb->slot_of_row, vvalid, values->offset, n, gb->pass0_off, k16, swz);
+        else hipLaunchKernelGGL((k_acc_part_keys<b(), false>), dim3(ntiles), dim3(kSortBlock), 0, st, gb->slot_of_row, vvalid, values->offset, n, gb->pass0_off, k16, swz);
+      });
       PDX_LAUNCH_CHECK();
       desc += " sort=part_keys:" + std::to_string(g.b0);
     }

@@ -197,31 +197,16 @@ static int build_layout(pdx_groupby* gb, const pdx_column* values, bool allow_fu
       if (!k8 || !nv0 || !nv1) return PDX_OOM;
       PDX_SCRATCH_CHECK(s);
       int rcn = PDX_OK;
-#define NARROW_P0(B)                                                                                                                         \
-  rcn = vvalid ? radix_scatter_narrow<B, uint64_t, uint32_t, uint16_t, true>(gb->slot_of_row, vin, k16, nv0, n, gb->pass0_off, st, vvalid, values->offset) \
-               : radix_scatter_narrow<B, uint64_t, uint32_t, uint16_t>(gb->slot_of_row, vin, k16, nv0, n, gb->pass0_off, st)
       if (fp.narrow_part) rcn = radix_scatter_only<kPartBits, uint64_t, uint8_t>(gb->bucket8, vin, nullptr, nv0, n, 0, false, gb->part_off, st);
       else
-        switch (b0) {
-          case 4: NARROW_P0(4); break;
-          case 5: NARROW_P0(5); break;
-          case 6: NARROW_P0(6); break;
-          case 7: NARROW_P0(7); break;
-          default: NARROW_P0(8); break;
-        }
-#undef NARROW_P0
+        rcn = with_digit_bits<4, 8>(b0, [&](auto b) {
+          return vvalid ? radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t, true>(gb->slot_of_row, vin, k16, nv0, n, gb->pass0_off, st, vvalid, values->offset)
+                        : radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t>(gb->slot_of_row, vin, k16, nv0, n, gb->pass0_off, st);
+        });
       PDX_TRY(rcn);
       // pass 1 in two halves: its offsets first -- the run starts and the longest run (the host needs that number to choose the
       // reducer) follow from them alone -- then the scatter, which runs while the host reads the number back
-#define NARROW_P1_OFFSETS(B) rcn = radix_offsets<B, uint16_t>(k16, n, 0, nhist, nchunk, true, st)
-      switch (b1) {
-        case 4: NARROW_P1_OFFSETS(4); break;
-        case 5: NARROW_P1_OFFSETS(5); break;
-        case 6: NARROW_P1_OFFSETS(6); break;
-        case 7: NARROW_P1_OFFSETS(7); break;
-        default: NARROW_P1_OFFSETS(8); break;
-      }
-#undef NARROW_P1_OFFSETS
+      rcn = with_digit_bits<4, 8>(b1, [&](auto b) { return radix_offsets<b(), uint16_t>(k16, n, 0, nhist, nchunk, true, st); });
       PDX_TRY(rcn);
       struct EventGuard {  // the event must not outlive an early return
         hipEvent_t ev = nullptr;
@@ -238,17 +223,10 @@ static int build_layout(pdx_groupby* gb, const pdx_column* values, bool allow_fu
         PDX_HIP(hipEventCreateWithFlags(&hmax_ready.ev, hipEventDisableTiming));
         PDX_HIP(hipEventRecord(hmax_ready.ev, st));
       }
-#define NARROW_P1(B)                                                                    \
-    rcn = vvalid ? radix_scatter_narrow<B, uint64_t, uint16_t, uint8_t, true>(k16, nv0, k8, nv1, n, nhist, st) \
-                 : radix_scatter_narrow<B, uint64_t, uint16_t, uint8_t>(k16, nv0, k8, nv1, n, nhist, st)
-      switch (b1) {
-        case 4: NARROW_P1(4); break;
-        case 5: NARROW_P1(5); break;
-        case 6: NARROW_P1(6); break;
-        case 7: NARROW_P1(7); break;
-        default: NARROW_P1(8); break;
-      }
-#undef NARROW_P1
+      rcn = with_digit_bits<4, 8>(b1, [&](auto b) {
+        return vvalid ? radix_scatter_narrow<b(), uint64_t, uint16_t, uint8_t, true>(k16, nv0, k8, nv1, n, nhist, st)
+                      : radix_scatter_narrow<b(), uint64_t, uint16_t, uint8_t>(k16, nv0, k8, nv1, n, nhist, st);
+      });
       PDX_TRY(rcn);
       {
         const hipError_t ew = hipEventSynchronize(hmax_ready.ev);

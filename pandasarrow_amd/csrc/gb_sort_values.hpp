@@ -40,13 +40,9 @@ static int sort_values_by_slot(pdx_groupby* gb, const uint64_t* vals, const uint
     if (gb->digit2) {  // second partition level: one more stable scatter with the stored digits / offsets
       uint64_t* vals_part2 = static_cast<uint64_t*>(alloc((size_t)n * 8));
       if (!vals_part2) return PDX_OOM;
-      switch (gb->digit2_bits) {
-        case 4: PDX_TRY((radix_scatter_only<4, uint64_t, uint8_t>(gb->digit2, vals_part, nullptr, vals_part2, n, 0, false, gb->part_off2, st))); break;
-        case 5: PDX_TRY((radix_scatter_only<5, uint64_t, uint8_t>(gb->digit2, vals_part, nullptr, vals_part2, n, 0, false, gb->part_off2, st))); break;
-        case 6: PDX_TRY((radix_scatter_only<6, uint64_t, uint8_t>(gb->digit2, vals_part, nullptr, vals_part2, n, 0, false, gb->part_off2, st))); break;
-        case 7: PDX_TRY((radix_scatter_only<7, uint64_t, uint8_t>(gb->digit2, vals_part, nullptr, vals_part2, n, 0, false, gb->part_off2, st))); break;
-        default: PDX_TRY((radix_scatter_only<8, uint64_t, uint8_t>(gb->digit2, vals_part, nullptr, vals_part2, n, 0, false, gb->part_off2, st))); break;
-      }
+      PDX_TRY((with_digit_bits<4, 8>(gb->digit2_bits, [&](auto b) {
+        return radix_scatter_only<b(), uint64_t, uint8_t>(gb->digit2, vals_part, nullptr, vals_part2, n, 0, false, gb->part_off2, st);
+      })));
       vals_part = vals_part2;
     }
     const uint32_t* kin = gb->slot_part;
@@ -77,20 +73,13 @@ static int sort_values_by_slot(pdx_groupby* gb, const uint64_t* vals, const uint
 template <typename K, typename KO, bool FLAGS = false>
 static int narrow_pass(int bits, const K* kin, const uint64_t* vin, KO* kout, uint64_t* vout, int64_t n, const uint32_t* offsets, uint32_t* hist,
                        uint32_t* chunk_sum, hipStream_t st, const uint8_t* valid = nullptr, int64_t valid_off = 0) {
-#define NARROW_PASS(B)                                                                                   \
-  {                                                                                                      \
-    if (!offsets) PDX_TRY((radix_offsets<B, K>(kin, n, 0, hist, chunk_sum, true, st)));                    \
-    return radix_scatter_narrow<B, uint64_t, K, KO, FLAGS>(kin, vin, kout, vout, n, offsets ? offsets : hist, st, valid, valid_off); \
-  }
-  switch (bits) {
-    case 4: NARROW_PASS(4)
-    case 5: NARROW_PASS(5)
-    case 6: NARROW_PASS(6)
-    case 7: NARROW_PASS(7)
-    case 8: NARROW_PASS(8)
-    default: return fail(PDX_INVALID, "narrowing sort: unsupported digit width");
-  }
-#undef NARROW_PASS
+  return with_digit_bits<4, 8>(
+      bits,
+      [&](auto b) {
+        if (!offsets) PDX_TRY((radix_offsets<b(), K>(kin, n, 0, hist, chunk_sum, true, st)));
+        return radix_scatter_narrow<b(), uint64_t, K, KO, FLAGS>(kin, vin, kout, vout, n, offsets ? offsets : hist, st, valid, valid_off);
+      },
+      [] { return fail(PDX_INVALID, "narrowing sort: unsupported digit width"); });
 }
 // Full stable sort of the values by dense slot with narrowing keys (three passes: 4 -> 2 -> 1 byte keys -> none) and every group's
 // offset from the scatter offsets (two levels of k_level_starts): 22 + 19 + 17 B/row instead of 3 x 24 + 2 x 4 (histograms) and no
@@ -107,14 +96,9 @@ struct NarrowTwo {
   int low_bits = 0, last_bits = 0;
 };
 static int last_digit_offsets(int bits, const uint8_t* k8, int64_t n, uint32_t* hist, uint32_t* chunk, hipStream_t st) {
-  switch (bits) {
-    case 4: return radix_offsets<4, uint8_t>(k8, n, 0, hist, chunk, true, st);
-    case 5: return radix_offsets<5, uint8_t>(k8, n, 0, hist, chunk, true, st);
-    case 6: return radix_offsets<6, uint8_t>(k8, n, 0, hist, chunk, true, st);
-    case 7: return radix_offsets<7, uint8_t>(k8, n, 0, hist, chunk, true, st);
-    case 8: return radix_offsets<8, uint8_t>(k8, n, 0, hist, chunk, true, st);
-    default: return fail(PDX_INVALID, "narrowing sort: unsupported digit width");
-  }
+  return with_digit_bits<4, 8>(
+      bits, [&](auto b) { return radix_offsets<b(), uint8_t>(k8, n, 0, hist, chunk, true, st); },
+      [] { return fail(PDX_INVALID, "narrowing sort: unsupported digit width"); });
 }
 static int finish_narrow_sort(const NarrowTwo& two, int64_t n, Scratch& s, hipStream_t st) {
   const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);

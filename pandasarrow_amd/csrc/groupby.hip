@@ -16,8 +16,9 @@
 //      (k_hash_bucket_hist + radix scatter; a second level for very many groups) -> one workgroup per bucket builds the
 //      bucket's table region in LDS (k_hash_probe_lds; skewed buckets: head rows there, the rest in chunks against an LDS
 //      snapshot, k_hash_probe_lds_tail; k_hash_probe_part is the memory-side fallback).  Tiny inputs: one global
-//      open-addressing table (k_hash_insert).
-//   2. occupied slots are compacted (slot order) and sorted by first_row -> dense gid in FIRST-OCCURRENCE order.
+//      open-addressing table (k_hash_insert).  Host side: gb_create.hpp, one builder per path (try_dense_speculative,
+//      try_dense_exact, build_hash_partitioned, build_hash_global), each returning a SlotDomain.
+//   2. occupied slots are compacted (slot order) and sorted by first_row -> dense gid in FIRST-OCCURRENCE order (finish_group_ids).
 //   3. per aggregated column: stable LSD radix sort of (slot, value) by slot (radix_sort.hpp) -> every group's values
 //      contiguous IN ROW ORDER.  For sum/mean/min/max/count (and variance) the last 6 slot bits are not sorted: k_flr_reduce
 //      ranks each 2560-row tile by them in LDS, stages the rows by 16-value leaf, sums one leaf per thread and pushes the leaves
@@ -157,6 +158,7 @@ static unsigned int* hmax_pinned() {
 namespace pdx {
 #include "gb_layout.hpp"
 #include "gb_acc.hpp"
+#include "gb_create.hpp"
 }  // namespace pdx
 
 extern "C" {
@@ -179,549 +181,33 @@ int pdx_groupby_create(const pdx_column* key, void* stream, pdx_groupby** out) {
     return PDX_OK;
   }
   Scratch s;
-  const long long* keys = static_cast<const long long*>(key->values) + key->offset;
-  const uint8_t* valid = validity_or_null(key);
-  HashCtl* ctl = s.get<HashCtl>(1);
+  const CreateTuning t = CreateTuning::read();
+  const CreateCtx c{gb, static_cast<const long long*>(key->values) + key->offset, validity_or_null(key), key->offset, n, s, st, t, s.get<HashCtl>(1)};
   if (s.failed) return PDX_OOM;
-  // ---- keys that arrive grouped (non-decreasing, no nulls: a sorted id column, a time index rounded to calendar bins): the groups
-  // are the runs of equal keys where they stand -- no dictionary, and no value sort in pdx_groupby_agg (segments mode, as resample).
-  // 65536 sampled neighbour pairs rule the path out for anything else at the price of one small kernel; the counting pass of the
-  // run-start compaction then proves the order over all rows (a sample that lied costs that one pass: the build below takes over).
-  const bool sorted_env = [] { const char* e = getenv("PDX_GROUPBY_SORTED"); return !(e && e[0] == '0'); }();
-  const char* denv = getenv("PDX_GROUPBY_DENSE");
-  const bool allow_dense = !(denv && denv[0] == '0');
-  const bool lds_ok = [] { const char* e = getenv("PDX_DENSE_LDS"); return !(e && e[0] == '0'); }();
-  const bool spec_ok = [] { const char* e = getenv("PDX_DENSE_SPECULATE"); return !(e && e[0] == '0'); }();
-  const bool want_sorted_sample = sorted_env && n >= 2 && !valid;
-  const bool want_range_sample = allow_dense && spec_ok && lds_ok && n >= ((int64_t)1 << 23);  // (the speculative dense build below)
-  KeyRange hsv[64];
-  unsigned int hflags[4] = {0, 0, 0, 4u};
-  unsigned int* flags = nullptr;
-  if (want_sorted_sample || want_range_sample) {  // both samples, one host round trip
-    flags = s.get<unsigned int>(4);
-    KeyRange* dsample = s.get<KeyRange>(64);
-    if (s.failed) return PDX_OOM;
-    if (want_sorted_sample) {
-      PDX_HIP(hipMemsetAsync(flags, 0, 4 * sizeof(unsigned int), st));
-      hipLaunchKernelGGL(k_sample_descents, dim3(64), dim3(1024), 0, st, keys, valid, key->offset, n, flags + 3);
-      PDX_HIP(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, st));
-    }
-    if (want_range_sample) {
-      hipLaunchKernelGGL(k_sample_key_range, dim3(64), dim3(1024), 0, st, keys, valid, key->offset, n, dsample);
-      PDX_HIP(hipMemcpyAsync(hsv, dsample, sizeof(hsv), hipMemcpyDeviceToHost, st));
-    }
-    PDX_LAUNCH_CHECK();
-    PDX_HIP(hipStreamSynchronize(st));
-  }
-  if (want_sorted_sample && !(hflags[3] & 4u) && (hflags[3] & 3u) != 3u) {
+  // both samples in one host round trip: sortedness (the runs path) and the key range (the speculative dense build)
+  const bool want_sorted_sample = t.sorted && n >= 2 && !c.valid;
+  const bool want_range_sample = t.dense && t.dense_speculate && t.dense_lds && n >= ((int64_t)1 << 23);
+  KeySample sample;
+  PDX_TRY(sample_keys(c, want_sorted_sample, want_range_sample, &sample));
+  if (sample.maybe_sorted) {
     bool done = false;
-    PDX_TRY(build_label_runs(gb, n, KeyLabel{keys}, 0, s, st, &done));
+    PDX_TRY(build_label_runs(gb, n, KeyLabel{c.keys}, 0, s, st, &done));
     if (done) {
       *out = owner.release();
       return PDX_OK;
     }
   }
-  // ---- dense-domain fast path: valid keys span a small integer range -> slot = key - min (or its residue form), no table
-  Slot* table = nullptr;
-  unsigned int* dense_first = nullptr;
-  long long dense_min = 0;
-  unsigned int dense_mask = 0;
-  unsigned int null_slot = 0;
-  int64_t nslots = 0;
-  const unsigned long long dense_lim = std::min<unsigned long long>(1ull << 26, (unsigned long long)n * 4 + 1024);
-
-  // Builds slot_of_row, first[] and (when the first sort digit is 4..8 bits wide) the scanned pass-0 offsets for the dense domain
-  // described by (mn, mask, null_slot, nslots).  range_out != nullptr: also the exact key range, computed by the same pass.
-  auto dense_build = [&](long long mn, unsigned int mask, KeyRange* range_out) -> int {
-    dense_first = s.get<unsigned int>((size_t)nslots);
-    if (s.failed) return PDX_OOM;
-    hipMemsetAsync(dense_first, 0xFF, (size_t)nslots * sizeof(unsigned int), st);
-    // prefix with the full first-row protocol, then the bitmap-filtered tail; the tail kernel is tile shaped and also emits the
-    // per-tile histogram of the first sort digit
-    const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);
-    const int bits0 = make_sort_plan(ilog2((uint64_t)nslots), sort_max_bits()).bits[0];
-    // rows that go through the full first-row protocol before the tail's bitmap is taken: a slot unseen by then costs one global atomic per
-    // later row of its key.  16 rows per slot leave e^-16 of uniformly spread keys unseen; below 2^29 rows 8 per slot (e^-8 = 3e-4 of the
-    // slots, a few 10^4 atomics) -- the prefix pass is the slow one (60 Grows/s: a random read of first[] per row) and at an 8-GPU shard's
-    // size 16 per slot was 13 % of the rows, 0.28 ms of a 0.84 ms create.
-    // From 2^29 rows on, domains whose bitmap fits the LDS tail (<= 2^20 slots) take 4 per slot: an unseen slot there costs a read of the
-    // cache-resident first[] per later row and an atomic only for the first of them.  Measured at 1e9 rows / 1e6 keys, the slot kernels
-    // per step over five alternated runs each: 16 -> 2.51-2.57 ms, 8 -> 2.46-2.52 ms, 4 -> 2.37-2.45 ms (at 1e5 keys the 2^22-row floor
-    // below decides and the three are the same 2.35 ms).  Larger domains (global bitmap, first[] not cache resident) keep 16.
-    const int64_t per_slot = [n, this_nslots = nslots] {
-      const char* e = getenv("PDX_DENSE_PREFIX_PER_SLOT");
-      if (e && atoi(e) > 0) return (int64_t)atoi(e);
-      if (n < ((int64_t)1 << 29)) return (int64_t)8;
-      return ((this_nslots + 31) >> 5) <= kDenseLdsWords ? (int64_t)4 : (int64_t)16;
-    }();
-    int64_t prefix = std::min<int64_t>(n, std::max<int64_t>((int64_t)1 << 22, per_slot * nslots));
-    prefix = std::min<int64_t>(n, round_up(prefix, kSortTile));
-    const bool fuse = bits0 >= 4 && bits0 <= 8;
-    const int64_t nwords = (nslots + 31) >> 5;
-    const int64_t tile_first_tail = prefix / kSortTile;
-    const bool lds_bitmap = fuse && lds_ok && prefix < n && nwords <= kDenseLdsWords && ntiles - tile_first_tail >= 256;
-    if (range_out && !(fuse && prefix < n)) return fail(PDX_DEVICE, "dense_build: fused key range needs the histogram tail");
-    uint32_t* chunk_sum = nullptr;
-    if (fuse) {
-      gb->pass0_off = gb->own<uint32_t>((size_t)ntiles << bits0);
-      chunk_sum = s.get<uint32_t>((size_t)(nchunks + 1) << bits0);  // + digit totals row
-      if (!gb->pass0_off || s.failed) return PDX_OOM;
-    }
-    KeyRange* wg_range = nullptr;
-    long long *tile_min = nullptr, *tile_max = nullptr;
-    if (range_out) {
-      wg_range = s.get<KeyRange>((size_t)kCUs);
-      if (s.failed) return PDX_OOM;
-      if (!lds_bitmap) {  // the global-bitmap tail writes one (min, max) per tile
-        tile_min = s.get<long long>((size_t)ntiles);
-        tile_max = s.get<long long>((size_t)ntiles);
-        if (s.failed) return PDX_OOM;
-      }
-    }
-    {
-      PDX_PROFILE("dense_slots", st);
-      // (a tail that walks all tiles from 0 rewrites every slot: the prefix then leaves slot_of_row alone)
-      if (prefix < n && fuse && (lds_bitmap || range_out))
-        hipLaunchKernelGGL(k_dense_slots<false>, dim3(grid_for(prefix, 256, 8)), dim3(256), 0, st, keys, valid, key->offset, prefix, mn, mask, null_slot,
-                           dense_first, gb->slot_of_row);
-      else
-        hipLaunchKernelGGL(k_dense_slots<true>, dim3(grid_for(prefix, 256, 8)), dim3(256), 0, st, keys, valid, key->offset, prefix, mn, mask, null_slot,
-                           dense_first, gb->slot_of_row);
-      if (prefix < n) {
-        uint32_t* seen = s.get<uint32_t>((size_t)nwords);
-        if (s.failed) return PDX_OOM;
-        hipLaunchKernelGGL(k_seen_bitmap, dim3(grid_for(nwords, 256)), dim3(256), 0, st, dense_first, nslots, seen);
-        const unsigned tail_tiles = (unsigned)(ntiles - tile_first_tail);
-        // the LDS tail walks ALL tiles (slots, histogram and key range of the prefix rows too; first-row tracking from `prefix` on)
-#define TAIL_HIST(B)                                                                                                                              \
-  if (lds_bitmap)                                                                                                                                 \
-    hipLaunchKernelGGL((k_dense_slots_tail_hist_lds<B>), dim3(kCUs), dim3(kDenseLdsBlock), 0, st, keys, valid, key->offset, (int64_t)0, ntiles, n,  \
-                       mn, mask, null_slot, seen, (int)nwords, prefix, dense_first, gb->slot_of_row, gb->pass0_off, wg_range);                    \
-  else if (range_out) /* all tiles: slots, histogram and key range of the prefix rows too */                                                     \
-    hipLaunchKernelGGL((k_dense_slots_tail_hist<B>), dim3((unsigned)ntiles), dim3(kSortBlock), 0, st, keys, valid, key->offset, (int64_t)0, n, mn,  \
-                       mask, null_slot, seen, prefix, dense_first, gb->slot_of_row, gb->pass0_off, tile_min, tile_max);                           \
-  else                                                                                                                                            \
-    hipLaunchKernelGGL((k_dense_slots_tail_hist<B>), dim3(tail_tiles), dim3(kSortBlock), 0, st, keys, valid, key->offset, tile_first_tail, n, mn,  \
-                       mask, null_slot, seen, prefix, dense_first, gb->slot_of_row, gb->pass0_off, (long long*)nullptr, (long long*)nullptr)
-        if (!fuse)
-          hipLaunchKernelGGL(k_dense_slots_tail, dim3(grid_for(n - prefix, 256, 8)), dim3(256), 0, st, keys, valid, key->offset, prefix, n, mn, mask,
-                             null_slot, seen, dense_first, gb->slot_of_row);
-        else if (bits0 == 4) TAIL_HIST(4);
-        else if (bits0 == 5) TAIL_HIST(5);
-        else if (bits0 == 6) TAIL_HIST(6);
-        else if (bits0 == 7) TAIL_HIST(7);
-        else TAIL_HIST(8);
-#undef TAIL_HIST
-      }
-    }
-    PDX_LAUNCH_CHECK();
-    if (fuse) {
-      if (!lds_bitmap && !range_out) {
-        // histogram of the prefix tiles (the prefix is a whole number of tiles unless it is the whole input)
-#define PREFIX_HIST(B) hipLaunchKernelGGL((k_radix_hist<B>), dim3((unsigned)ceil_div(prefix, kSortTile)), dim3(kSortBlock), 0, st, gb->slot_of_row, prefix, 0, \
-                                          gb->pass0_off)
-        if (bits0 == 4) PREFIX_HIST(4);
-        else if (bits0 == 5) PREFIX_HIST(5);
-        else if (bits0 == 6) PREFIX_HIST(6);
-        else if (bits0 == 7) PREFIX_HIST(7);
-        else PREFIX_HIST(8);
-#undef PREFIX_HIST
-      }
-      int rcs = radix_scan_dispatch(bits0, gb->pass0_off, ntiles, chunk_sum, true, st);
-      if (rcs != PDX_OK) return rcs;
-    }
-    if (range_out && !lds_bitmap) {
-      long long lo = 0, hi = 0, dummy = 0;
-      PDX_TRY(minmax_i64_host(tile_min, ntiles, &lo, &dummy, s, st));
-      PDX_TRY(minmax_i64_host(tile_max, ntiles, &dummy, &hi, s, st));
-      *range_out = KeyRange{lo, hi, lo <= hi ? 1 : 0, 0};
-    } else if (range_out) {
-      std::vector<KeyRange> h((size_t)kCUs);
-      PDX_HIP(hipMemcpyAsync(h.data(), wg_range, sizeof(KeyRange) * kCUs, hipMemcpyDeviceToHost, st));
-      PDX_HIP(hipStreamSynchronize(st));
-      KeyRange r{0x7FFFFFFFFFFFFFFFll, (long long)0x8000000000000000ull, 0, 0};
-      for (size_t wi = 0; wi < h.size(); ++wi)
-        if (h[wi].any) {
-          r.vmin = std::min(r.vmin, h[wi].vmin);
-          r.vmax = std::max(r.vmax, h[wi].vmax);
-          r.any = 1;
-        }
-      *range_out = r;
-    }
-    return PDX_OK;
-  };
-
-  MinMaxPartial<long long> mm;
-  bool have_mm = false;
-  bool sample_rules_out_dense = !allow_dense;
-  // ---- speculative single pass: guess the width of the key window from a sample, build the residue-form dense domain and the
-  // exact min/max together (saves the separate 8 B/row min/max pass), accept when the exact span fits the guessed width
-  if (want_range_sample) {
-    KeyRange hs{0x7FFFFFFFFFFFFFFFll, (long long)0x8000000000000000ull, 0, 0};
-    for (const KeyRange& w : hsv)
-      if (w.any) {
-        hs.vmin = std::min(hs.vmin, w.vmin);
-        hs.vmax = std::max(hs.vmax, w.vmax);
-        hs.any = 1;
-      }
-    int b = 64;
-    if (hs.any) {
-      const unsigned long long span_s = (unsigned long long)hs.vmax - (unsigned long long)hs.vmin;
-      b = 4;
-      while (b < 64 && (span_s >> b)) ++b;  // smallest width (>= 4 bits) with sample span < 2^b
-      // the sample range lies inside the exact range: a sample already too wide for the dense domain settles the question
-      // without the full min/max pass
-      if (span_s >= dense_lim) sample_rules_out_dense = true;
-    }
-    // Only windows of <= 20 bits (LDS-resident bitmap).  Wider windows work too (global bitmap, tile min/max in the same pass) but
-    // do not pay: the power-of-two residue domain makes the bitmap up to 2x larger than key - min and costs more than the
-    // saved min/max pass (measured at 1e7 keys: 42.6 vs 39.7 ms).
-    const int spec_max_bits = [] { const char* e = getenv("PDX_DENSE_SPECULATE_BITS"); return e ? atoi(e) : 20; }();
-    if (b <= spec_max_bits && b <= 26 && (1ull << b) <= dense_lim && (int64_t)16 * (((int64_t)1 << b) + 1) + 2 * kSortTile < n) {
-      dense_mask = (1u << b) - 1;
-      null_slot = 1u << b;
-      nslots = (int64_t)null_slot + (valid ? 1 : 0);
-      gb->slot_of_row = gb->own<uint32_t>((size_t)n);
-      if (!gb->slot_of_row) return PDX_OOM;
-      KeyRange exact;
-      PDX_TRY(dense_build(0, dense_mask, &exact));
-      mm.vmin = exact.vmin;
-      mm.vmax = exact.vmax;
-      mm.rmin = mm.rmax = exact.any ? 0 : -1;
-      have_mm = true;
-      if (exact.any && (unsigned long long)exact.vmax - (unsigned long long)exact.vmin <= dense_mask) {
-        gb->dense = 1;
-        dense_min = exact.vmin;
-      } else {
-        // the window is wider than the sample suggested (or there is no valid key at all): redo on the exact range below
-        dense_mask = 0;
-        dense_first = nullptr;
-        while (!gb->owned.empty()) {
-          pool_free(gb->owned.back());
-          gb->owned.pop_back();
-        }
-        gb->slot_of_row = nullptr;
-        gb->pass0_off = nullptr;
-      }
-    }
+  // key -> slot: dense slots when the keys span a small integer range (speculatively, then on the exact range), else a hash table
+  SlotDomain d;
+  KeyRangeFacts range;
+  range.not_dense = !t.dense;
+  if (want_range_sample) PDX_TRY(try_dense_speculative(c, sample.range, &d, &range));
+  if (!gb->dense && !range.not_dense) PDX_TRY(try_dense_exact(c, &d, &range));
+  if (!gb->dense) {
+    const bool use_partition = t.partition != 0 && (n >= ((int64_t)1 << 18) || t.partition == 2);
+    PDX_TRY(use_partition ? build_hash_partitioned(c, &d) : build_hash_global(c, &d));
   }
-  if (!gb->dense && !sample_rules_out_dense) {
-    if (!have_mm) {
-      int rc0 = minmax_keys_host(keys, valid, key->offset, n, &mm, s, st);
-      if (rc0 != PDX_OK) return rc0;
-    }
-    if (allow_dense && mm.rmin >= 0) {
-      unsigned long long span = (unsigned long long)mm.vmax - (unsigned long long)mm.vmin;  // range - 1
-      if (span < dense_lim) {
-        gb->dense = 1;
-        dense_min = mm.vmin;
-        null_slot = (unsigned int)span + 1;
-        nslots = (int64_t)null_slot + 1;
-      }
-    } else if (allow_dense && mm.rmin < 0) {  // every key is null: one group
-      gb->dense = 1;
-      null_slot = 0;
-      nslots = 1;
-    }
-    if (gb->dense) {
-      gb->slot_of_row = gb->own<uint32_t>((size_t)n);
-      if (!gb->slot_of_row) return PDX_OOM;
-      PDX_TRY(dense_build(dense_min, 0, nullptr));
-    }
-  }
-  unsigned int region = 0;  // != 0: partitioned hash table (logical slot = (index in region << kPartBits) | bucket)
-  const char* penv = getenv("PDX_HASH_PARTITION");
-  const bool use_partition = !gb->dense && !(penv && penv[0] == '0') && (n >= ((int64_t)1 << 18) || (penv && penv[0] == '2'));
-  if (!use_partition && !gb->dense) {
-    gb->slot_of_row = gb->own<uint32_t>((size_t)n);
-    if (!gb->slot_of_row) return PDX_OOM;
-  }
-  if (gb->dense) {
-    // (built above)
-  } else if (use_partition) {
-    // ---- general keys, partitioned build: hash -> stable partition by the low 8 hash bits (== first LSD pass of the sort by slot)
-    const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);
-    gb->bucket8 = gb->own<uint8_t>((size_t)n);
-    gb->part_off = gb->own<uint32_t>((size_t)ntiles << kPartBits);
-    gb->slot_part = gb->own<uint32_t>((size_t)n);
-    // row ids ride through the partition only when there are null keys (their flag is bit 31 of the row id); otherwise on demand
-    const bool rows_in_partition = valid != nullptr || [] { const char* e = getenv("PDX_HASH_ROWS"); return e && e[0] == '1'; }();
-    if (rows_in_partition) gb->rows_part = gb->own<uint32_t>((size_t)n);
-    gb->idx16_part = gb->own<uint16_t>((size_t)n);
-    bool idx16_written = false;  // by the attempt that succeeded (the LDS build at the first partition level)
-    uint32_t* chunk_sum = s.get<uint32_t>((size_t)(nchunks + 1) << kPartBits);  // + digit totals row
-    long long* keys_part = s.get<long long>((size_t)n);
-    if (s.failed || !gb->bucket8 || !gb->part_off || !gb->slot_part || (rows_in_partition && !gb->rows_part) || !gb->idx16_part) return PDX_OOM;
-    {
-      // one pass over the keys: bucket byte per row (kept: it is the digit of the value partition of every later aggregation)
-      // + the partition histogram
-      PDX_PROFILE("hash_bucket_hist", st);
-      hipLaunchKernelGGL(k_hash_bucket_hist, dim3((unsigned)ntiles), dim3(kSortBlock), 0, st, keys, valid, key->offset, n, gb->bucket8, gb->part_off);
-    }
-    int rcp = radix_scan_only<kPartBits>(gb->part_off, ntiles, chunk_sum, true, st);
-    if (rcp == PDX_OK && rows_in_partition)  // keys and row ids in ONE scatter (they used to be two kernels ranking the same bucket bytes: 5.0 + 2.5 ms per 1e9 rows)
-      rcp = radix_scatter_with_rows<kPartBits>(gb->bucket8, reinterpret_cast<const uint64_t*>(keys), reinterpret_cast<uint64_t*>(keys_part),
-                                               gb->rows_part, n, gb->part_off, valid, key->offset, st);
-    else if (rcp == PDX_OK)  // the keys alone: 17 instead of 21 B/row, and the pass of the value partition (4 waves per SIMD)
-      rcp = radix_scatter_only<kPartBits, uint64_t, uint8_t>(gb->bucket8, reinterpret_cast<const uint64_t*>(keys), nullptr, reinterpret_cast<uint64_t*>(keys_part), n,
-                                                             0, false, gb->part_off, st);
-    if (rcp != PDX_OK) return rcp;
-    uint64_t want = std::max<uint64_t>(next_pow2((uint64_t)n * 2), 1u << 16);
-    unsigned int cap = (unsigned int)std::min<uint64_t>(want, 1u << 21);
-    unsigned int pb = kPartBits;              // hash bits the rows are currently partitioned by
-    uint32_t* bucket_starts = nullptr;        // starts of the 2^pb buckets after a second partition level
-    bool lds_failed_at_pb = false;
-    for (;;) {
-      table = static_cast<Slot*>(pool_alloc(((size_t)cap + 2) * sizeof(Slot)));
-      if (!table) return PDX_OOM;
-      region = cap >> pb;
-      hipLaunchKernelGGL(k_table_init, dim3(grid_for((int64_t)cap + 2, 256, 4)), dim3(256), 0, st, table, (int64_t)cap + 2);
-      hipMemsetAsync(ctl, 0, sizeof(HashCtl), st);
-      unsigned int limit = (unsigned int)((uint64_t)cap * 7 / 10);
-      const char* lenv = getenv("PDX_HASH_LDS");
-      const bool use_lds = region <= (unsigned)kLdsRegionMax && !(lenv && lenv[0] == '0') && !lds_failed_at_pb;
-      if (use_lds) {
-        PDX_PROFILE("hash_probe_lds", st);
-        // bucket starts: the offsets row of tile 0 of the partition pass, or the searched starts after a second level
-        // skewed buckets (longer than 1.5x the average and 2^20 rows): head rows here, the rest in chunks (k_hash_probe_lds_tail)
-        const uint32_t* boff = bucket_starts ? bucket_starts : gb->part_off;
-        const size_t nb = (size_t)1 << pb;
-        int64_t head_rows = std::max<int64_t>((int64_t)1 << 20, (n >> pb) + (n >> (pb + 1)));
-        if (const char* e = getenv("PDX_HASH_HEAD_ROWS")) head_rows = std::max<int64_t>(atoll(e), 1);
-        head_rows = (head_rows + 4 * kProbeBlock - 1) / (4 * kProbeBlock) * (4 * kProbeBlock);
-        std::vector<TailChunk> chunks;
-        if (n > head_rows) {
-          std::vector<uint32_t> hoff(nb);
-          PDX_HIP(hipMemcpyAsync(hoff.data(), boff, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-          PDX_HIP(hipStreamSynchronize(st));
-          for (size_t bi = 0; bi < nb; ++bi) {
-            const int64_t bs = hoff[bi], be = bi + 1 < nb ? (int64_t)hoff[bi + 1] : n;
-            for (int64_t c0 = bs + head_rows; c0 < be; c0 += kTailChunkRows)
-              chunks.push_back(TailChunk{(uint32_t)bi, (uint32_t)c0, (uint32_t)std::min<int64_t>(c0 + kTailChunkRows, be)});
-          }
-        }
-        uint16_t* idx16 = pb == (unsigned)kPartBits ? gb->idx16_part : nullptr;
-        idx16_written = idx16 != nullptr;
-        if (!chunks.empty() || pb != (unsigned)kPartBits) PDX_TRY(ensure_rows_part(gb, st));  // (the tail kernel tracks first rows per row)
-        const bool first_as_pos = !valid && !gb->rows_part;
-        if (valid)
-          hipLaunchKernelGGL((k_hash_probe_lds<true>), dim3(1u << pb), dim3(kProbeBlock), 0, st, keys_part, gb->rows_part, boff, n, table, cap, region,
-                             gb->slot_part, ctl, pb, head_rows, idx16);
-        else  // no null keys: rows_part is not read per row (first rows as positions), and with idx16 the 4-byte slot is not written
-          hipLaunchKernelGGL((k_hash_probe_lds<false>), dim3(1u << pb), dim3(kProbeBlock), 0, st, keys_part, gb->rows_part, boff, n, table, cap, region,
-                             gb->slot_part, ctl, pb, head_rows, idx16);
-        if (first_as_pos)
-          hipLaunchKernelGGL(k_first_rows_from_pos, dim3((unsigned)(((int64_t)cap + 2 + 255) / 256)), dim3(256), 0, st, table, cap, region,
-                             gb->part_off, ntiles, gb->bucket8, n);
-        if (!chunks.empty()) {
-          TailChunk* dchunks = s.get<TailChunk>(chunks.size());
-          if (s.failed) {
-            pool_free(table);
-            return PDX_OOM;
-          }
-          PDX_HIP(hipMemcpyAsync(dchunks, chunks.data(), chunks.size() * sizeof(TailChunk), hipMemcpyHostToDevice, st));
-          hipLaunchKernelGGL(k_hash_probe_lds_tail, dim3((unsigned)chunks.size()), dim3(kProbeBlock), 0, st, keys_part, gb->rows_part, dchunks, table, cap,
-                             region, gb->slot_part, ctl, pb, idx16);
-          PDX_HIP(hipStreamSynchronize(st));  // `chunks` (pageable host memory) must outlive the copy
-        }
-      } else {
-        idx16_written = false;
-        PDX_TRY(ensure_rows_part(gb, st));
-        PDX_PROFILE("hash_probe_part", st);
-        constexpr unsigned int kWindowBits = 16;  // 2^16 slots = 1 MB per bucket window; about two buckets are active at a time
-        const unsigned int nsweeps = region > (1u << kWindowBits) ? region >> kWindowBits : 1u;
-        for (unsigned int sw = 0; sw < nsweeps; ++sw)
-          hipLaunchKernelGGL((k_hash_probe_part<4>), dim3((unsigned int)ceil_div(n, 1024 * kProbeTiles)), dim3(256), 0, st, keys_part, gb->rows_part, n, table,
-                             cap, region, limit, gb->slot_part, ctl, nsweeps > 1 ? kWindowBits : 31u, sw, pb);
-      }
-      HashCtl h;
-      hipError_t e = hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) {
-        pool_free(table);
-        return hip_fail(e, "k_hash_probe_part");
-      }
-      if (getenv("PDX_HASH_DEBUG"))
-        fprintf(stderr, "[pdx] hash build attempt: pb=%u cap=%u region=%u lds=%d inserted=%u overflow=%u rows_seen=%llu distinct_seen=%llu\n", pb, cap,
-                region, (int)use_lds, h.inserted, h.overflow, (unsigned long long)h.rows_seen, (unsigned long long)h.est_distinct);
-      if (!h.overflow && h.inserted <= limit) break;
-      pool_free(table);
-      table = nullptr;
-      if (cap >= want * 4 || cap >= (1u << 30)) return fail(PDX_DEVICE, "pdx_groupby_create: hash table overflow at maximum capacity");
-      if (use_lds && pb > (unsigned)kPartBits) lds_failed_at_pb = true;  // a skewed bucket outgrew LDS even after the split: memory-side build
-      uint64_t next = (uint64_t)cap * 8;
-      double groups = 0.0;
-      if (h.rows_seen) {
-        // the LDS attempt saw d distinct keys in its first r rows (an exact pair, taken after every bucket's first 4096 rows):
-        // size the retry for the cardinality K that predicts, d = K (1 - exp(-r / K)) for uniformly mixed keys.  Too few
-        // repeats to tell means "more groups than the sample can resolve": plan for min(n, 2^28) keys.
-        const double d = (double)h.est_distinct, r = (double)h.rows_seen;
-        groups = std::min((double)n, 268435456.0);
-        if (r - d > 0.001 * r && r - d >= 512.0) {
-          double lo = d, hi = 1e18;  // bisection on K
-          for (int it = 0; it < 200; ++it) {
-            double mid = std::sqrt(lo * hi);
-            if (mid * -std::expm1(-r / mid) < d) lo = mid;
-            else hi = mid;
-          }
-          groups = std::min((double)n, hi * -std::expm1(-(double)n / hi));
-        }
-        next = std::max<uint64_t>(next, next_pow2((uint64_t)(groups / 0.4) + 1));  // aim at <= 40 % load: the estimate is noisy
-      }
-      // Very many groups: instead of a table that falls out of the L2 (every probe and atomic then goes to memory: 1.4 s per 1e9
-      // rows measured), split the buckets by a second partition level until a bucket's table (<= 8192 slots at <= ~35 % load)
-      // fits in LDS again.  The second level is one more stable scatter of (key, row) by the next hash bits; the logical slot id
-      // keeps the (index << pb) | bucket form with pb = 8 + extra, so the later sort by slot just sees a longer partitioned prefix.
-      const bool split_ok = [] { const char* e = getenv("PDX_HASH_SPLIT"); return !(e && e[0] == '0'); }();
-      if (split_ok && pb == (unsigned)kPartBits && groups > 0.0 && next > (1u << 21) && !(lenv && lenv[0] == '0')) {
-        int extra = 4;
-        while (extra < 8 && groups / (double)((uint64_t)1 << (kPartBits + extra)) > 2800.0) ++extra;  // ~35 % load when there is room ...
-        if (groups / (double)((uint64_t)1 << (kPartBits + extra)) <= 4200.0) {  // ... up to ~51 % at the last level (2.7e8 groups)
-          const int64_t ntiles2 = ntiles, nchunks2 = nchunks;
-          PDX_TRY(ensure_rows_part(gb, st));
-          gb->digit2 = gb->own<uint8_t>((size_t)n);
-          gb->part_off2 = gb->own<uint32_t>((size_t)ntiles2 << extra);
-          uint32_t* chunk_sum2 = s.get<uint32_t>((size_t)(nchunks2 + 1) << extra);
-          long long* keys_part2 = s.get<long long>((size_t)n);
-          uint32_t* rows_part2 = gb->own<uint32_t>((size_t)n);
-          bucket_starts = s.get<uint32_t>(((size_t)1 << (kPartBits + extra)) + 1);
-          if (s.failed || !gb->digit2 || !gb->part_off2 || !rows_part2) return PDX_OOM;
-          int rc2 = PDX_OK;
-          {
-            PDX_PROFILE("hash_bucket_hist", st);
-#define DIGIT_HIST(B) hipLaunchKernelGGL((k_hash_digit_hist<B>), dim3((unsigned)ntiles2), dim3(kSortBlock), 0, st, keys_part, gb->rows_part, n, kPartBits, \
-                                         gb->digit2, gb->part_off2)
-            switch (extra) {
-              case 4: DIGIT_HIST(4); break;
-              case 5: DIGIT_HIST(5); break;
-              case 6: DIGIT_HIST(6); break;
-              case 7: DIGIT_HIST(7); break;
-              default: DIGIT_HIST(8); break;
-            }
-#undef DIGIT_HIST
-          }
-          rc2 = radix_scan_dispatch(extra, gb->part_off2, ntiles2, chunk_sum2, true, st);
-#define SCATTER2(B)                                                                                                                                   \
-  if (rc2 == PDX_OK)                                                                                                                                  \
-    rc2 = radix_scatter_only<B, uint64_t, uint8_t>(gb->digit2, reinterpret_cast<const uint64_t*>(keys_part), nullptr,                                   \
-                                                   reinterpret_cast<uint64_t*>(keys_part2), n, 0, false, gb->part_off2, st);                           \
-  if (rc2 == PDX_OK) rc2 = radix_scatter_only<B, uint32_t, uint8_t>(gb->digit2, gb->rows_part, nullptr, rows_part2, n, 0, false, gb->part_off2, st)
-          switch (extra) {
-            case 4: SCATTER2(4); break;
-            case 5: SCATTER2(5); break;
-            case 6: SCATTER2(6); break;
-            case 7: SCATTER2(7); break;
-            default: SCATTER2(8); break;
-          }
-#undef SCATTER2
-          if (rc2 != PDX_OK) return rc2;
-          keys_part = keys_part2;
-          gb->rows_part = rows_part2;  // (the first-level array stays owned by the handle until it is destroyed)
-          pb = kPartBits + extra;
-          gb->digit2_bits = extra;
-          hipLaunchKernelGGL(k_bucket_starts, dim3(grid_for((int64_t)1 << pb, 256)), dim3(256), 0, st, keys_part, gb->rows_part, n, pb, bucket_starts);
-          PDX_LAUNCH_CHECK();
-          cap = (unsigned int)kLdsRegionMax << pb;
-          continue;
-        }
-      }
-      cap = (unsigned int)std::min<uint64_t>(std::max<uint64_t>(next, (uint64_t)cap * 2), std::max<uint64_t>(want * 4, 1u << 16));
-    }
-    gb->part_bits = (int)pb;
-    if (!idx16_written) gb->idx16_part = nullptr;  // (the block stays owned by the handle; nothing reads it)
-    gb->slot_part_ready = !idx16_written;          // the LDS build at the first level writes the 2-byte region indexes only
-    gb->owned.push_back(table);
-    {
-      Slot sp[2];
-      PDX_HIP(hipMemcpyAsync(sp, table + cap, sizeof(sp), hipMemcpyDeviceToHost, st));
-      PDX_HIP(hipStreamSynchronize(st));
-      gb->special_slots = sp[0].first != kNoRow || sp[1].first != kNoRow;
-    }
-    null_slot = cap;
-    nslots = (int64_t)cap + 2;
-  } else {
-  // table capacity: start at min(2^21, pow2 >= 2n) and grow x8 whenever more than 70 % of the slots fill up
-  uint64_t want = next_pow2((uint64_t)n * 2);
-  unsigned int cap = (unsigned int)std::min<uint64_t>(want, 1u << 21);
-  for (;;) {
-    table = static_cast<Slot*>(pool_alloc(((size_t)cap + 2) * sizeof(Slot)));
-    if (!table) return PDX_OOM;
-    hipLaunchKernelGGL(k_table_init, dim3(grid_for((int64_t)cap + 2, 256, 4)), dim3(256), 0, st, table, (int64_t)cap + 2);
-    hipMemsetAsync(ctl, 0, sizeof(HashCtl), st);
-    unsigned int limit = (unsigned int)((uint64_t)cap * 7 / 10);
-    if (cap >= want) limit = cap;  // a table of >= 2n slots can never overflow
-    {
-      PDX_PROFILE("hash_insert", st);
-      hipLaunchKernelGGL(k_hash_insert, dim3(grid_for(n, 256, 8)), dim3(256), 0, st, keys, valid, key->offset, n, table, cap, limit,
-                         gb->slot_of_row, ctl);
-    }
-    HashCtl h;
-    hipError_t e = hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        pool_free(table);
-        return hip_fail(e, "k_hash_insert");
-      }
-    if (!h.overflow) break;
-    pool_free(table);
-    if (cap >= want) return fail(PDX_DEVICE, "pdx_groupby_create: hash table overflow at maximum capacity");
-    cap = (unsigned int)std::min<uint64_t>((uint64_t)cap * 8, want);
-  }
-  gb->owned.push_back(table);
-  null_slot = cap;
-  nslots = (int64_t)cap + 2;
-  }
-  gb->nslots = nslots;
-  gb->slot_bits = ilog2((uint64_t)nslots);
-  gb->gid_of_slot = gb->own<uint32_t>((size_t)nslots);
-  // occupied slots in slot order
-  uint32_t* occ_slot_tmp = s.get<uint32_t>((size_t)std::min<int64_t>(nslots, n + 2));
-  uint32_t* occ_first_tmp = s.get<uint32_t>((size_t)std::min<int64_t>(nslots, n + 2));
-  if (s.failed || !gb->gid_of_slot) return PDX_OOM;
-  int64_t G = 0;
-  int rc = compact_indices(nslots, OccPred{table, dense_first, region, null_slot}, OccEmit{table, dense_first, region, null_slot, occ_slot_tmp, occ_first_tmp},
-                           &G, s, st);
-  if (rc != PDX_OK) return rc;
-  gb->G = G;
-  gb->occ_slot = gb->own<uint32_t>((size_t)G);
-  gb->gid_of_occ = gb->own<uint32_t>((size_t)G);
-  gb->uniques = gb->own<int64_t>((size_t)G);
-  gb->unique_ok = gb->own<uint8_t>((size_t)G);
-  gb->first_rows = gb->own<int64_t>((size_t)G);
-  if (s.failed || !gb->occ_slot || !gb->gid_of_occ || !gb->uniques || !gb->unique_ok || !gb->first_rows) return PDX_OOM;
-  hipMemcpyAsync(gb->occ_slot, occ_slot_tmp, (size_t)G * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
-  // order groups by first occurrence: gid = rank of the group's first row among all first rows (bit map + block prefix, no sort).
-  // Nearly every row its own group: the random bit sets / word reads of the map cost more than sorting the (first row, slot)
-  // pairs (measured at 1.5e8 groups of 2.5e8 rows, pdx_reindex_indices: 65 ms with the map -- 5.6 ms of bit sets, > 10 ms of rank
-  // reads -- against 54 ms with the sort)
-  const bool rank_by_sort = G > ((int64_t)1 << 22) && G * 8 > n;
-  if (rank_by_sort) {
-    uint32_t* k0 = s.get<uint32_t>((size_t)G);
-    uint32_t* v0 = s.get<uint32_t>((size_t)G);
-    uint32_t* k1 = s.get<uint32_t>((size_t)G);
-    uint32_t* v1 = s.get<uint32_t>((size_t)G);
-    PDX_SCRATCH_CHECK(s);
-    const uint32_t *ks = nullptr, *vs = nullptr;  // sort (first_row -> slot); first rows are distinct so any order of ties is moot
-    rc = radix_sort_pairs<uint32_t>(occ_first_tmp, occ_slot_tmp, k0, v0, k1, v1, G, ilog2((uint64_t)n + 1) < 31 ? ilog2((uint64_t)n + 1) : 31, &ks, &vs,
-                                    true, s, st);
-    if (rc != PDX_OK) return rc;
-    const int g = grid_for(G, 256);
-    hipLaunchKernelGGL(k_assign_gids, dim3(g), dim3(256), 0, st, table, dense_min, dense_mask, gb->gid_of_slot, ks, vs, G, null_slot, gb->uniques,
-                       gb->unique_ok, gb->first_rows, region);
-    hipLaunchKernelGGL(k_gid_of_occ, dim3(g), dim3(256), 0, st, gb->gid_of_slot, gb->occ_slot, G, gb->gid_of_occ);
-  } else {
-    const int64_t nwords = (n + 63) >> 6, nrb = ceil_div(nwords, (int64_t)kRankWords);
-    unsigned long long* bits = s.get<unsigned long long>((size_t)nwords);
-    int64_t* block_pre = s.get<int64_t>((size_t)nrb);
-    PDX_SCRATCH_CHECK(s);
-    PDX_HIP(hipMemsetAsync(bits, 0, (size_t)nwords * sizeof(unsigned long long), st));
-    const int g = grid_for(G, 256);
-    hipLaunchKernelGGL(k_mark_first_rows, dim3(g), dim3(256), 0, st, occ_first_tmp, G, bits);
-    hipLaunchKernelGGL(k_rank_block_counts, dim3(grid_for(nrb * kRankWords, 256)), dim3(256), 0, st, bits, nwords, nrb, block_pre);
-    PDX_TRY((device_exclusive_scan<int64_t, SumOp>(block_pre, block_pre, nrb, (int64_t*)nullptr, s, st)));
-    hipLaunchKernelGGL(k_assign_gids_ranked, dim3(g), dim3(256), 0, st, table, dense_min, dense_mask, gb->gid_of_slot, occ_first_tmp, occ_slot_tmp, G, bits,
-                       block_pre, null_slot, gb->uniques, gb->unique_ok, gb->first_rows, region, gb->gid_of_occ);
-  }
+  PDX_TRY(finish_group_ids(c, d));
   hipError_t e = hipGetLastError();
   // no drain of the stream: everything the caller can read on the host (G) is known; later calls are ordered by the stream / the event
   if (e == hipSuccess) e = hipEventCreateWithFlags(&gb->ready, hipEventDisableTiming);
@@ -1546,8 +1032,7 @@ int pdx_downsample_create(const pdx_column* ts, int64_t multiple, int unit, int 
   if (n > 0x7FFFFFFFll) return fail(PDX_NOT_IMPLEMENTED, "pdx_downsample_create: more than 2^31-1 rows per call is not supported yet");
   hipStream_t st = as_stream(stream);
   *out = nullptr;
-  const bool runs_env = [] { const char* e = getenv("PDX_GROUPBY_SORTED"); return !(e && e[0] == '0'); }();
-  if (runs_env && n >= 1 && !validity_or_null(ts)) {
+  if (CreateTuning::read().sorted && n >= 1 && !validity_or_null(ts)) {
     std::unique_ptr<pdx_groupby> owner(new pdx_groupby());
     owner->stream = st;
     pdx_groupby* gb = owner.get();
@@ -1557,22 +1042,10 @@ int pdx_downsample_create(const pdx_column* ts, int64_t multiple, int unit, int 
     const long long* t = static_cast<const long long*>(ts->values) + ts->offset;
     bool done = false;
     int rc = PDX_OK;
-#define DS_RUNS(M)                                                                                      \
-  rc = ceil_mode ? build_label_runs(gb, n, RoundLabel<M, true>{t, q}, label_shift_ns, s, st, &done)     \
-                 : build_label_runs(gb, n, RoundLabel<M, false>{t, q}, label_shift_ns, s, st, &done)
-    switch (mode) {
-      case 0: DS_RUNS(0); break;
-      case 1: DS_RUNS(1); break;
-      case 2: DS_RUNS(2); break;
-      case 3: DS_RUNS(3); break;
-      case 4: DS_RUNS(4); break;
-      case 5: DS_RUNS(5); break;
-      case 6: DS_RUNS(6); break;
-      case 7: DS_RUNS(7); break;
-      case 8: DS_RUNS(8); break;
-      default: DS_RUNS(9); break;
-    }
-#undef DS_RUNS
+    rc = with_digit_bits<0, 9>(mode, [&](auto m) {  // (the rounding mode is a template parameter too)
+      return ceil_mode ? build_label_runs(gb, n, RoundLabel<m(), true>{t, q}, label_shift_ns, s, st, &done)
+                       : build_label_runs(gb, n, RoundLabel<m(), false>{t, q}, label_shift_ns, s, st, &done);
+    });
     if (rc != PDX_OK) return rc;
     if (done) {
       *out = owner.release();

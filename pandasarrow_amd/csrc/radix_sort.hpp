@@ -554,15 +554,24 @@ int radix_scan_only(uint32_t* hist, int64_t ntiles, uint32_t* chunk_sum, bool bi
   PDX_LAUNCH_CHECK();
   return PDX_OK;
 }
-inline int radix_scan_dispatch(int bits, uint32_t* hist, int64_t ntiles, uint32_t* chunk_sum, bool big, hipStream_t st) {
-  switch (bits) {
-    case 4: return radix_scan_only<4>(hist, ntiles, chunk_sum, big, st);
-    case 5: return radix_scan_only<5>(hist, ntiles, chunk_sum, big, st);
-    case 6: return radix_scan_only<6>(hist, ntiles, chunk_sum, big, st);
-    case 7: return radix_scan_only<7>(hist, ntiles, chunk_sum, big, st);
-    case 8: return radix_scan_only<8>(hist, ntiles, chunk_sum, big, st);
-    default: return fail(PDX_INVALID, "radix sort: unsupported digit width");
+// The digit width (a template parameter of the kernels) from a run-time value: f(std::integral_constant<int, B>{}) for the B in
+// [LO, HI] that equals `bits`; any other width goes to other().  Without `other`, HI takes them (the widest digit).
+template <int LO, int HI, typename F, typename Other>
+auto with_digit_bits(int bits, F&& f, Other&& other) -> decltype(f(std::integral_constant<int, HI>{})) {
+  if constexpr (LO > HI) {
+    return other();
+  } else {
+    if (bits == LO) return f(std::integral_constant<int, LO>{});
+    return with_digit_bits<LO + 1, HI>(bits, f, other);
   }
+}
+template <int LO, int HI, typename F>
+auto with_digit_bits(int bits, F&& f) -> decltype(f(std::integral_constant<int, HI>{})) {
+  return with_digit_bits<LO, HI>(bits, f, [&] { return f(std::integral_constant<int, HI>{}); });
+}
+inline int bad_digit_width() { return fail(PDX_INVALID, "radix sort: unsupported digit width"); }
+inline int radix_scan_dispatch(int bits, uint32_t* hist, int64_t ntiles, uint32_t* chunk_sum, bool big, hipStream_t st) {
+  return with_digit_bits<4, 8>(bits, [&](auto b) { return radix_scan_only<b()>(hist, ntiles, chunk_sum, big, st); }, bad_digit_width);
 }
 // per-tile digit histogram + column scan
 template <int BITS, typename K = uint32_t>
@@ -704,29 +713,15 @@ int radix_pass(const uint32_t* kin, const V* vin, uint32_t* kout, V* vout, int64
 template <typename V>
 int radix_pass_dispatch(int bits, const uint32_t* kin, const V* vin, uint32_t* kout, V* vout, int64_t n, int shift, bool write_keys,
                         uint32_t* hist, uint32_t* chunk_sum, hipStream_t st) {
-  switch (bits) {
-    case 4: return radix_pass<4, V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st);
-    case 5: return radix_pass<5, V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st);
-    case 6: return radix_pass<6, V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st);
-    case 7: return radix_pass<7, V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st);
-    case 8: return radix_pass<8, V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st);
-    case 9: return radix_pass<9, V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st);
-    case 10: return radix_pass<10, V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st);
-    default: return fail(PDX_INVALID, "radix sort: unsupported digit width");
-  }
+  return with_digit_bits<4, 10>(
+      bits, [&](auto b) { return radix_pass<b(), V>(kin, vin, kout, vout, n, shift, write_keys, hist, chunk_sum, st); }, bad_digit_width);
 }
 
 template <typename V>
 int radix_scatter_dispatch(int bits, const uint32_t* kin, const V* vin, uint32_t* kout, V* vout, int64_t n, int shift, bool write_keys,
                            const uint32_t* offsets, hipStream_t st) {
-  switch (bits) {
-    case 4: return radix_scatter_only<4, V>(kin, vin, kout, vout, n, shift, write_keys, offsets, st);
-    case 5: return radix_scatter_only<5, V>(kin, vin, kout, vout, n, shift, write_keys, offsets, st);
-    case 6: return radix_scatter_only<6, V>(kin, vin, kout, vout, n, shift, write_keys, offsets, st);
-    case 7: return radix_scatter_only<7, V>(kin, vin, kout, vout, n, shift, write_keys, offsets, st);
-    case 8: return radix_scatter_only<8, V>(kin, vin, kout, vout, n, shift, write_keys, offsets, st);
-    default: return fail(PDX_INVALID, "radix sort: unsupported digit width");
-  }
+  return with_digit_bits<4, 8>(
+      bits, [&](auto b) { return radix_scatter_only<b(), V>(kin, vin, kout, vout, n, shift, write_keys, offsets, st); }, bad_digit_width);
 }
 inline int sort_max_bits() {
   int max_bits = 8;

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+from _create_plans import pinned_slots
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +92,7 @@ def test_groupby_fuzz(px, monkeypatch, seed, mode):
     uk, uok = gb.unique_keys().to_numpy()
     assert np.array_equal(np.ones(G, bool) if uok is None else uok, ~isnull) and np.array_equal(uk[~isnull], uniq[~isnull])
     outs = gb.agg(px.Column.from_numpy(vals, vvalid, offset=int(seed % 5)), kinds)
+    assert gb.last_plan()["slots"] == pinned_slots("groupby_fuzz", seed, mode)
     for kind, out in zip(kinds, outs):
         got, ok = out.to_numpy()
         exp, eok = orc.groupby_agg(kind, ids, G, vals, vvalid, nthreads=4)
@@ -132,6 +134,7 @@ def test_groupby_fuzz_bound_columns(px, monkeypatch, seed, mode):
     for k in kinds:
         check(k, gb.agg(vcol, [k])[0], "single")
         assert gb.last_plan()["bound"] == "1"
+        assert gb.last_plan()["slots"] == pinned_slots("groupby_fuzz_bound_columns", seed, mode)
     for k, out in zip(kinds, gb.agg(vcol, kinds)):
         check(k, out, "together")
     for k in reversed(kinds):

@@ -1,10 +1,13 @@
 """GPU parity tests (run with `-m gpu` on an MI355X).  Every check goes HIP kernels -> C ABI (libpdx_hip.so) -> ctypes,
 and is compared bit-for-bit with the CPU oracle and with the committed golden vectors (Arrow 25.0.0 outputs and the
 reference's own known-answer tests).  Tolerances: none -- integer, index and fp64 results must be bit-identical."""
+import os
+
 import numpy as np
 import pytest
 
 import oracle as orc
+from _create_plans import pinned_slots
 from conftest import assert_f64_bits, golden
 
 pytestmark = pytest.mark.gpu
@@ -329,6 +332,7 @@ def test_groupby_golden(px, monkeypatch, name, hashmode):
             continue
         vcol = px.Column.from_numpy(c[keyname], vvalid, offset=2)
         outs = gb.agg(vcol, list(GB.values()))  # all five from one grouped pass
+        assert gb.last_plan()["slots"] == pinned_slots("groupby_golden", name, hashmode)
         for (k, kind), out in zip(GB.items(), outs):
             vals, ok = out.to_numpy()
             exp = c[f"{col}_{k}"]
@@ -396,6 +400,7 @@ def test_groupby_sizes_vs_oracle(px, monkeypatch, n, nk, dense):
     keys, vals = orc.synth_keys(0, n, nk), orc.synth_vals(0, n) - 0.5
     gb = px.K.GroupByHandle.create(px.Column.from_numpy(keys))
     s, m, cnt, lo, hi = gb.agg(px.Column.from_numpy(vals), [0, 1, 4, 2, 3])
+    assert gb.last_plan()["slots"] == pinned_slots("groupby_sizes_vs_oracle", n, nk, dense, os.environ.get("PDX_HASH_PARTITION", "default"))
     ek, es, em, ec = orc.groupby_sum_mean_count(keys, vals, nthreads=8)
     assert np.array_equal(gb.unique_keys().to_numpy()[0], ek)
     assert np.array_equal(cnt.to_numpy()[0], ec)
@@ -422,6 +427,7 @@ def test_groupby_skewed_vs_oracle(px, monkeypatch, n, nk, dtype, dense):
     gb = px.K.GroupByHandle.create(px.Column.from_numpy(keys))
     ids, uniq, _, _ = orc.group_ids(keys)
     outs = gb.agg(px.Column.from_numpy(vals), [0, 1, 4, 2, 3])
+    assert gb.last_plan()["slots"] == pinned_slots("groupby_skewed_vs_oracle", n, nk, dtype, dense)
     assert np.array_equal(gb.unique_keys().to_numpy()[0], uniq)
     for out, kind in zip(outs, (orc.AGG_SUM, orc.AGG_MEAN, orc.AGG_COUNT, orc.AGG_MIN, orc.AGG_MAX)):
         got = out.to_numpy()[0]
@@ -453,6 +459,7 @@ def test_groupby_dense_with_nulls_and_negative_keys(px, monkeypatch, dense):
     assert np.array_equal(uok, ~isnull) and np.array_equal(uk[uok], uniq[~isnull])
     assert np.array_equal(gb.first_rows().cpu().numpy(), first)
     s = gb.agg(px.Column.from_numpy(vals), [0])[0].to_numpy()[0]
+    assert gb.last_plan()["slots"] == pinned_slots("groupby_dense_with_nulls_and_negative_keys", dense, os.environ.get("PDX_HASH_PARTITION", "default"))
     assert_f64_bits(s, orc.groupby_agg(orc.AGG_SUM, ids, len(uniq), vals)[0])
 
 
@@ -612,6 +619,7 @@ def test_groupby_next_aggs_golden(px, monkeypatch, name, hashmode):
             continue
         vcol = px.Column.from_numpy(c[keyname], vvalid, offset=2)
         outs = gb.agg(vcol, [0] + list(GB_NEXT.values()))  # together with a standard kind in one call
+        assert gb.last_plan()["slots"] == pinned_slots("groupby_next_aggs_golden", name, hashmode)
         for (k, kind), out in zip(GB_NEXT.items(), outs[1:]):
             vals, ok = out.to_numpy()
             exp = c[f"{col}_{k}"]
@@ -679,6 +687,7 @@ def test_groupby_split_partition_special_keys(px, monkeypatch):
     assert np.array_equal(uok, ~isnull) and np.array_equal(uk[uok], uniq[~isnull])
     assert np.array_equal(gb.first_rows().cpu().numpy(), first)
     s, c, mx = gb.agg(px.Column.from_numpy(vals, vvalid), [0, 4, 3])
+    assert gb.last_plan()["slots"] == pinned_slots("groupby_split_partition_special_keys")
     for out, kind in ((s, 0), (c, 4), (mx, 3)):
         got, ok = out.to_numpy()
         exp, eok = orc.groupby_agg(kind, ids, len(uniq), vals, vvalid, nthreads=8)
@@ -687,6 +696,30 @@ def test_groupby_split_partition_special_keys(px, monkeypatch):
             assert_f64_bits(got, exp, valid=eok, what=str(kind))
         else:
             assert np.array_equal(got[eok], exp[eok])
+
+
+@pytest.mark.parametrize("keyform", ["dense", "hashed"])
+def test_groupby_sort_ranked_first_occurrence(px, monkeypatch, keyform):
+    """every row its own group and more than 2^22 of them (G > 2^22 and 8 G > n): the groups' first-occurrence order comes from a sort
+    of the (first row, slot) pairs instead of the first-row bitmap.  n = 2^22 + 4097 is the smallest shape that takes the branch with a
+    ragged last sort tile; a fixed permutation of 0..n-1 as it is (dense slots), and spread by an odd factor (hash table)."""
+    monkeypatch.setenv("PDX_GROUPBY_SORTED", "0")  # a permutation is never sorted, but the runs path must not be a matter of luck
+    n = (1 << 22) + 4097
+    keys = np.random.default_rng(422).permutation(n).astype(np.int64)
+    if keyform == "hashed":
+        monkeypatch.setenv("PDX_GROUPBY_DENSE", "0")
+        keys = keys * 1_000_003 - 987_654_321
+    vals = orc.synth_vals(0, n) - 0.5
+    gb = px.K.GroupByHandle.create(px.Column.from_numpy(keys))
+    ids, uniq, _, first = orc.group_ids(keys)
+    assert gb.num_groups == len(uniq) == n
+    assert np.array_equal(gb.unique_keys().to_numpy()[0], uniq)
+    assert np.array_equal(gb.first_rows().cpu().numpy(), first)
+    assert np.array_equal(gb.group_ids().cpu().numpy().astype(np.uint32), ids)
+    s = gb.agg(px.Column.from_numpy(vals), [0])[0].to_numpy()[0]
+    slots = gb.last_plan()["slots"]
+    assert (slots == "dense") if keyform == "dense" else slots.startswith("hash"), slots
+    assert_f64_bits(s, orc.groupby_agg(orc.AGG_SUM, ids, len(uniq), vals, nthreads=8)[0], what="sum")
 
 
 @pytest.mark.parametrize("narrow", ["default", "0"])
@@ -841,6 +874,7 @@ def test_groupby_hash_half_null_keys(px, monkeypatch, shape, head):
     assert np.array_equal(uok, ~isnull) and np.array_equal(uk[uok], uniq[~isnull])
     assert np.array_equal(gb.first_rows().cpu().numpy(), first)
     s, c = gb.agg(px.Column.from_numpy(vals), [0, 4])
+    assert gb.last_plan()["slots"] == pinned_slots("groupby_hash_half_null_keys", shape, head)
     for out, kind in ((s, 0), (c, 4)):
         got, ok = out.to_numpy()
         exp, eok = orc.groupby_agg(kind, ids, len(uniq), vals, None, nthreads=8)

@@ -2,7 +2,7 @@
 //
 // Reference: GroupBy's constructor materialises every column's per-group arrays once (processEach, src/dataframe.cpp:1539-1554:
 // Grouper::MakeGroupings + ApplyGroupings) and sum() / mean() / count() reuse them (src/group_by.h:85-139).  Here the same
-// split: build_layout sorts the values by slot (stage 1), the reducers in groupby.hip consume the layout (stage 2); a bound column
+// split: build_layout sorts the values by slot (stage 1), the reducers in gb_agg.hpp consume the layout (stage 2); a bound column
 // (pdx_groupby_bind) keeps its layout in the handle, so the reference's call pattern gb.sum(c); gb.mean(c); gb.count(c) sorts once.
 #pragma once
 
@@ -46,44 +46,6 @@ struct AggTuning {
 
 constexpr unsigned int kFlrMaxRun = 1u << 19;  // a run is walked by ONE workgroup / wave (and sizes their counter levels): longer runs
                                                // (skewed keys) go through the side form below, or the whole column takes the classic path
-
-// The side form of a fused layout: the rows of the (few) runs longer than t.max_run, gathered with their full slots, sorted by the top
-// digit (one pass: within a digit they are in run order already, so the result is in slot order) and cut into segments for all G
-// groups.  `keys` = the layout's top-digit bytes or 4-byte slots, `vals` its values, both sorted by the low slot bits.
-template <typename KT>
-static int build_side(pdx_groupby* gb, GroupedLayout& L, const KT* keys, const uint64_t* vals, const uint32_t* run_start, int64_t nruns, int low_bits,
-                      unsigned int limit, int n_long, int64_t rows_long, bool nullable, Scratch& s, hipStream_t st) {
-  PDX_PROFILE("side_layout", st);
-  const int64_t G = gb->G, m = rows_long;
-  uint32_t* unordered = s.get<uint32_t>(kMaxLongRuns);
-  uint32_t* list = s.get<uint32_t>(kMaxLongRuns);
-  uint32_t* off = s.get<uint32_t>(kMaxLongRuns + 1);
-  unsigned int* cnt = s.get<unsigned int>(1);
-  uint32_t* k_in = s.get<uint32_t>((size_t)m);
-  uint64_t* v_in = s.get<uint64_t>((size_t)m);
-  PDX_SCRATCH_CHECK(s);
-  uint32_t* k_out = L.own<uint32_t>((size_t)m);
-  uint64_t* v_out = L.own<uint64_t>((size_t)m);
-  uint32_t* seg = L.own<uint32_t>((size_t)G + 1);
-  if (!k_out || !v_out || !seg) return PDX_OOM;
-  PDX_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned int), st));
-  hipLaunchKernelGGL(k_long_runs_append, dim3(grid_for(nruns, 256)), dim3(256), 0, st, run_start, nruns, limit, (unsigned int)kMaxLongRuns, unordered, cnt);
-  hipLaunchKernelGGL(k_long_runs_order, dim3(1), dim3(256), 0, st, unordered, n_long, run_start, list, off);
-  hipLaunchKernelGGL((k_side_gather<KT>), dim3(grid_for(m, 256, 4)), dim3(256), 0, st, keys, vals, run_start, list, off, n_long, low_bits, m, k_in, v_in);
-  PDX_LAUNCH_CHECK();
-  const uint32_t* ks = nullptr;
-  const uint64_t* vs = nullptr;
-  PDX_TRY((radix_sort_pairs<uint64_t>(k_in, v_in, k_out, v_out, k_out, v_out, m, kFlrBits, &ks, &vs, true, s, st, low_bits)));
-  hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(G + 1, 256)), dim3(256), 0, st, ks, m, gb->occ_slot, G, seg);
-  PDX_LAUNCH_CHECK();
-  L.side_rows = m;
-  L.side_runs = n_long;
-  L.side_vals = vs;
-  L.side_seg = seg;
-  if (nullable) L.side_keys = ks;
-  else L.disown(k_out);
-  return PDX_OK;
-}
 
 // Which sort feeds the fused last digit on this handle (all false: full sort + classic reducers)
 struct FusedPlan {
@@ -142,228 +104,338 @@ static void keep_only(GroupedLayout& L, size_t mark, std::initializer_list<const
   for (void* q : drop) L.disown(q);
 }
 
+// What every piece of build_layout works on: the handle, the value column of the call and the layout under construction.  ONE Scratch
+// per build_layout call, released when the driver returns: k16, nhist, nchunk and dmax are read by kernels that a later piece enqueues.
+struct LayoutCtx {
+  pdx_groupby* gb;
+  const pdx_column* values;
+  const uint8_t* vvalid;  // the column's validity bitmap or nullptr
+  const uint64_t* vin;    // row 0 of its values
+  const AggTuning& t;
+  GroupedLayout& L;
+  Scratch& s;
+  hipStream_t st;
+};
+
+// The runs of a column sorted by its low slot bits, as k_run_max_len counts them
+struct RunStats {
+  unsigned int hmax = 0, n_long = 0, rows_long = 0;  // longest run, runs over the limit, their rows
+  // a few long runs (one key with a large share of the rows is enough to make one) are reduced from a side form, the rest by the
+  // fused kernels; many or very long ones: the whole column takes the classic path
+  bool side_ok(const AggTuning& t, int64_t n) const { return t.hybrid && n_long > 0 && n_long <= (unsigned int)kMaxLongRuns && (int64_t)rows_long <= n / 4; }
+};
+
+// What sort_narrow_to_runs / sort_lsd_to_runs return: the rows stably sorted by the low `low_bits` slot bits.  Every block named here
+// is owned by the layout except dmax, nhist and nchunk (scratch of the build_layout call).
+struct SortedRuns {
+  int low_bits = 0;
+  int64_t nruns = 0;
+  unsigned int max_run = 0;                      // rows of the longest run the fused kernels take
+  uint32_t* run_start = nullptr;                 // nruns + 1
+  unsigned int* dmax = nullptr;                  // the three words of RunStats on the device
+  const uint8_t* keys8 = nullptr;                // narrowing sort: the top digit of every row (else nullptr)
+  const uint32_t* fkeys = nullptr;               // 4-byte LSD: the slot of every row (else nullptr)
+  const uint64_t* vals = nullptr;
+  uint64_t* spare = nullptr;                     // narrowing sort: the values as pass 0 left them, free as the target of one more pass
+  uint32_t *nhist = nullptr, *nchunk = nullptr;  // narrowing sort: the offsets scratch of its passes
+  RunStats stats;
+  std::string sort_desc;
+};
+
+// (A') of GroupedLayout as build_side returns it (all zero: no run is over the limit)
+struct SideForm {
+  int64_t rows = 0;
+  int runs = 0;
+  const uint64_t* vals = nullptr;
+  const uint32_t *keys = nullptr, *seg = nullptr;
+};
+
+// seal_fused / seal_full: the only places that set L.fused / L.full, the field groups (A), (A'), (B) of GroupedLayout and its plan strings
+static int seal_fused(const LayoutCtx& c, const SortedRuns& r, const SideForm& side) {
+  GroupedLayout& L = c.L;
+  L.fused = true;
+  L.keys8 = r.keys8;
+  L.fkeys = r.fkeys;
+  L.fvals = r.vals;
+  if (r.spare) L.disown(r.spare);
+  L.low_bits = r.low_bits;
+  L.nruns = r.nruns;
+  L.hmax = std::min(r.stats.hmax, r.max_run);  // (rows of the longest run the fused kernels walk)
+  L.max_run = r.max_run;
+  L.run_start = r.run_start;
+  L.side_rows = side.rows;
+  L.side_runs = side.runs;
+  L.side_vals = side.vals;
+  L.side_keys = side.keys;
+  L.side_seg = side.seg;
+  L.plan_fused = std::string("slots=") + slots_name(c.gb) + " sort=" + r.sort_desc + " layout=fused" + (side.rows ? " side=" + std::to_string(side.runs) : std::string());
+  return PDX_OK;
+}
+static int seal_full(const LayoutCtx& c, const void* vals_sorted, const uint32_t* flag_keys, const uint32_t* seg_start, const uint32_t* out_index,
+                     const uint8_t* row_valid, const std::string& sort_desc, bool skew) {
+  GroupedLayout& L = c.L;
+  L.full = true;
+  L.vals_sorted = vals_sorted;
+  L.flag_keys = flag_keys;
+  L.seg_start = seg_start;
+  L.out_index = out_index;
+  L.row_valid = row_valid;
+  L.plan_full = std::string("slots=") + slots_name(c.gb) + " sort=" + sort_desc + " layout=full" + (skew ? " skew=1" : "");
+  return PDX_OK;
+}
+
+// segments: the rows are grouped as they stand
+static int layout_segments(const LayoutCtx& c) { return seal_full(c, c.vin, nullptr, c.gb->seg_start, nullptr, c.vvalid, "none", false); }
+
+// The side form of a fused layout: the rows of the (few) runs longer than r.max_run, gathered with their full slots, sorted by the top
+// digit (one pass: within a digit they are in run order already, so the result is in slot order) and cut into segments for all G
+// groups.  `keys` = the runs' top-digit bytes or 4-byte slots.
+template <typename KT>
+static int build_side(const LayoutCtx& c, const SortedRuns& r, const KT* keys, SideForm* out) {
+  pdx_groupby* gb = c.gb;
+  GroupedLayout& L = c.L;
+  Scratch& s = c.s;
+  hipStream_t st = c.st;
+  PDX_PROFILE("side_layout", st);
+  const int64_t G = gb->G, m = (int64_t)r.stats.rows_long;
+  const int n_long = (int)r.stats.n_long;
+  uint32_t* unordered = s.get<uint32_t>(kMaxLongRuns);
+  uint32_t* list = s.get<uint32_t>(kMaxLongRuns);
+  uint32_t* off = s.get<uint32_t>(kMaxLongRuns + 1);
+  unsigned int* cnt = s.get<unsigned int>(1);
+  uint32_t* k_in = s.get<uint32_t>((size_t)m);
+  uint64_t* v_in = s.get<uint64_t>((size_t)m);
+  PDX_SCRATCH_CHECK(s);
+  uint32_t* k_out = L.own<uint32_t>((size_t)m);
+  uint64_t* v_out = L.own<uint64_t>((size_t)m);
+  uint32_t* seg = L.own<uint32_t>((size_t)G + 1);
+  if (!k_out || !v_out || !seg) return PDX_OOM;
+  PDX_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned int), st));
+  hipLaunchKernelGGL(k_long_runs_append, dim3(grid_for(r.nruns, 256)), dim3(256), 0, st, r.run_start, r.nruns, r.max_run, (unsigned int)kMaxLongRuns, unordered, cnt);
+  hipLaunchKernelGGL(k_long_runs_order, dim3(1), dim3(256), 0, st, unordered, n_long, r.run_start, list, off);
+  hipLaunchKernelGGL((k_side_gather<KT>), dim3(grid_for(m, 256, 4)), dim3(256), 0, st, keys, r.vals, r.run_start, list, off, n_long, r.low_bits, m, k_in, v_in);
+  PDX_LAUNCH_CHECK();
+  const uint32_t* ks = nullptr;
+  const uint64_t* vs = nullptr;
+  PDX_TRY((radix_sort_pairs<uint64_t>(k_in, v_in, k_out, v_out, k_out, v_out, m, kFlrBits, &ks, &vs, true, s, st, r.low_bits)));
+  hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(G + 1, 256)), dim3(256), 0, st, ks, m, gb->occ_slot, G, seg);
+  PDX_LAUNCH_CHECK();
+  *out = SideForm{m, n_long, vs, nullptr, seg};
+  if (c.vvalid) out->keys = ks;
+  else L.disown(k_out);
+  return PDX_OK;
+}
+
+// both sorts to runs begin here: the run starts (kept by a fused layout) and the device words of RunStats
+static int begin_runs(const LayoutCtx& c, const FusedPlan& fp, SortedRuns* r) {
+  r->low_bits = fp.low_bits;
+  r->nruns = (int64_t)1 << fp.low_bits;
+  r->max_run = std::min(c.t.max_run, kFlrMaxRun);
+  r->run_start = c.L.own<uint32_t>((size_t)r->nruns + 1);
+  r->dmax = c.s.get<unsigned int>(3);
+  if (!r->run_start) return PDX_OOM;
+  PDX_SCRATCH_CHECK(c.s);
+  return PDX_OK;
+}
+
+// The narrowing sort (fp.narrow: dense slots, two passes; fp.narrow_part: the hash partition plays pass 0) up to the run statistics.
+// Returns with pass 1's scatter enqueued and the statistics read back; every block of both passes is still owned.
+static int sort_narrow_to_runs(const LayoutCtx& c, const FusedPlan& fp, SortedRuns* r) {
+  pdx_groupby* gb = c.gb;
+  GroupedLayout& L = c.L;
+  Scratch& s = c.s;
+  hipStream_t st = c.st;
+  const int64_t n = gb->n;
+  PDX_TRY(begin_runs(c, fp, r));
+  const int b0 = fp.narrow ? fp.low_plan.bits[0] : kPartBits, b1 = fp.narrow ? fp.low_plan.bits[1] : fp.mid_bits;
+  r->sort_desc = std::string(fp.narrow ? "narrow:" : "narrow_part:") + std::to_string(b0) + "+" + std::to_string(b1);
+  const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);
+  uint16_t* k16 = fp.narrow ? s.get<uint16_t>((size_t)n) : gb->idx16_part;
+  const uint32_t* prev_off = fp.narrow ? gb->pass0_off : gb->part_off;  // (row 0 = where every first digit's rows begin in the input of pass 1)
+  uint8_t* k8 = L.own<uint8_t>((size_t)n);
+  uint64_t* nv0 = L.own<uint64_t>((size_t)n);
+  uint64_t* nv1 = L.own<uint64_t>((size_t)n);
+  uint32_t* nhist = s.get<uint32_t>((size_t)ntiles << 8);
+  uint32_t* nchunk = s.get<uint32_t>((size_t)(nchunks + 1) << 8);
+  if (!k8 || !nv0 || !nv1) return PDX_OOM;
+  PDX_SCRATCH_CHECK(s);
+  int rcn = PDX_OK;
+  if (fp.narrow_part) rcn = radix_scatter_only<kPartBits, uint64_t, uint8_t>(gb->bucket8, c.vin, nullptr, nv0, n, 0, false, gb->part_off, st);
+  else
+    rcn = with_digit_bits<4, 8>(b0, [&](auto b) {
+      return c.vvalid ? radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t, true>(gb->slot_of_row, c.vin, k16, nv0, n, gb->pass0_off, st, c.vvalid, c.values->offset)
+                      : radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t>(gb->slot_of_row, c.vin, k16, nv0, n, gb->pass0_off, st);
+    });
+  PDX_TRY(rcn);
+  // pass 1 in two halves: its offsets first -- the run starts and the longest run (the host needs that number to choose the
+  // reducer) follow from them alone -- then the scatter, which runs while the host reads the number back
+  rcn = with_digit_bits<4, 8>(b1, [&](auto b) { return radix_offsets<b(), uint16_t>(k16, n, 0, nhist, nchunk, true, st); });
+  PDX_TRY(rcn);
+  struct EventGuard {  // the event must not outlive an early return
+    hipEvent_t ev = nullptr;
+    ~EventGuard() { if (ev) (void)hipEventDestroy(ev); }
+  } hmax_ready;
+  {
+    PDX_PROFILE("run_starts", st);
+    // (row 0 of the pass-0 offsets = where every first digit's rows begin in the input of pass 1)
+    hipLaunchKernelGGL((k_level_starts<uint16_t>), dim3(1u << b0), dim3(256), 0, st, k16, n, prev_off, (int64_t)1 << b0, b0, b1, nhist, r->run_start);
+    PDX_HIP(hipMemsetAsync(r->dmax, 0, 3 * sizeof(unsigned int), st));
+    hipLaunchKernelGGL(k_run_max_len, dim3(grid_for(r->nruns, 256)), dim3(256), 0, st, r->run_start, r->nruns, r->dmax, r->max_run);
+    PDX_LAUNCH_CHECK();
+    PDX_HIP(hipMemcpyAsync(hmax_pinned(), r->dmax, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    PDX_HIP(hipEventCreateWithFlags(&hmax_ready.ev, hipEventDisableTiming));
+    PDX_HIP(hipEventRecord(hmax_ready.ev, st));
+  }
+  rcn = with_digit_bits<4, 8>(b1, [&](auto b) {
+    return c.vvalid ? radix_scatter_narrow<b(), uint64_t, uint16_t, uint8_t, true>(k16, nv0, k8, nv1, n, nhist, st)
+                    : radix_scatter_narrow<b(), uint64_t, uint16_t, uint8_t>(k16, nv0, k8, nv1, n, nhist, st);
+  });
+  PDX_TRY(rcn);
+  const hipError_t ew = hipEventSynchronize(hmax_ready.ev);
+  if (ew != hipSuccess) return hip_fail(ew, "pdx_groupby_agg");
+  r->stats = RunStats{hmax_pinned()[0], hmax_pinned()[1], hmax_pinned()[2]};
+  r->keys8 = k8;
+  r->vals = nv1;
+  r->spare = nv0;
+  r->nhist = nhist;
+  r->nchunk = nchunk;
+  return PDX_OK;
+}
+
+// The narrowing sort on skewed keys: the fused kernel is skipped.  Finish the sort with the one pass that is left (on the byte digits)
+// and take the group offsets from its scatter offsets: one more level of k_level_starts gives the start of every slot's rows
+static int finish_narrow_skewed(const LayoutCtx& c, const SortedRuns& r) {
+  pdx_groupby* gb = c.gb;
+  GroupedLayout& L = c.L;
+  hipStream_t st = c.st;
+  const int64_t n = gb->n, G = gb->G;
+  uint32_t* ss_narrow = L.own<uint32_t>((size_t)G + 1);
+  uint32_t* slot_start = c.s.get<uint32_t>(((size_t)r.nruns << kFlrBits) + 1);
+  if (!ss_narrow) return PDX_OOM;
+  PDX_SCRATCH_CHECK(c.s);
+  PDX_TRY((radix_offsets<kFlrBits, uint8_t>(r.keys8, n, 0, r.nhist, r.nchunk, true, st)));
+  const uint32_t* fkeys = nullptr;
+  if (c.vvalid) {  // the classic nullable reducers read the null flag from bit 31 of a 4-byte key per grouped row: write flags only
+    uint32_t* fk = L.own<uint32_t>((size_t)n);
+    if (!fk) return PDX_OOM;
+    PDX_TRY((radix_scatter_narrow<kFlrBits, uint64_t, uint8_t, uint32_t, true>(r.keys8, r.vals, fk, r.spare, n, r.nhist, st)));
+    fkeys = fk;
+  } else {
+    PDX_TRY((radix_scatter_narrow<kFlrBits, uint64_t, uint8_t, uint8_t>(r.keys8, r.vals, (uint8_t*)nullptr, r.spare, n, r.nhist, st)));
+  }
+  {
+    PDX_PROFILE("seg_starts", st);
+    hipLaunchKernelGGL((k_level_starts<uint8_t>), dim3((unsigned)std::min<int64_t>(r.nruns, 65536)), dim3(256), 0, st, r.keys8, n, r.run_start, r.nruns,
+                       r.low_bits, kFlrBits, r.nhist, slot_start);
+    hipLaunchKernelGGL(k_seg_starts_from_slots, dim3(grid_for(G + 1, 256)), dim3(256), 0, st, slot_start, n, gb->occ_slot, G, ss_narrow);
+  }
+  PDX_LAUNCH_CHECK();
+  L.disown(r.keys8);  // what is kept of the sort: the values of the last pass, the group offsets, the flag keys
+  L.disown(r.vals);
+  L.disown(r.run_start);
+  return seal_full(c, r.spare, fkeys, ss_narrow, gb->gid_of_occ, nullptr, r.sort_desc, true);
+}
+
+// 4-byte slots sorted by the low bits only (LSD passes that skip the top digit), run starts by a search in the sorted slots
+static int sort_lsd_to_runs(const LayoutCtx& c, const FusedPlan& fp, SortedRuns* r) {
+  pdx_groupby* gb = c.gb;
+  GroupedLayout& L = c.L;
+  hipStream_t st = c.st;
+  PDX_TRY(begin_runs(c, fp, r));
+  r->sort_desc = "lsd:skip" + std::to_string(gb->slot_bits - r->low_bits);
+  const size_t mark = L.owned.size();
+  PDX_TRY(sort_values_by_slot(gb, c.vin, c.vvalid, c.values->offset, [&](size_t bytes) { return (void*)L.own<uint8_t>(bytes); }, c.s, st, &r->fkeys, &r->vals,
+                              gb->slot_bits - r->low_bits));
+  keep_only(L, mark, {r->fkeys, r->vals});
+  {
+    PDX_PROFILE("run_starts", st);
+    PDX_HIP(hipMemsetAsync(r->dmax, 0, 3 * sizeof(unsigned int), st));
+    hipLaunchKernelGGL(k_run_starts, dim3(grid_for(r->nruns + 1, 256)), dim3(256), 0, st, r->fkeys, gb->n, r->low_bits, r->nruns, r->run_start, r->dmax);
+    hipLaunchKernelGGL(k_run_max_len, dim3(grid_for(r->nruns, 256)), dim3(256), 0, st, r->run_start, r->nruns, r->dmax, r->max_run);
+    PDX_LAUNCH_CHECK();
+    unsigned int h3[3] = {0, 0, 0};
+    PDX_HIP(hipMemcpyAsync(h3, r->dmax, sizeof(h3), hipMemcpyDeviceToHost, st));
+    PDX_HIP(hipStreamSynchronize(st));
+    r->stats = RunStats{h3[0], h3[1], h3[2]};
+  }
+  return PDX_OK;
+}
+
+// The tail of every sort by the whole slot: group offsets by a search in the sorted slots, which then stay only as null flags
+static int finish_sorted_slots(const LayoutCtx& c, const uint32_t* keys_sorted, const uint64_t* vs, const std::string& sort_desc, bool skew) {
+  pdx_groupby* gb = c.gb;
+  const int64_t G = gb->G;
+  uint32_t* ss = c.L.own<uint32_t>((size_t)G + 1);
+  if (!ss) return PDX_OOM;
+  {
+    PDX_PROFILE("seg_starts", c.st);
+    hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(G + 1, 256)), dim3(256), 0, c.st, keys_sorted, gb->n, gb->occ_slot, G, ss);
+  }
+  PDX_LAUNCH_CHECK();
+  if (!c.vvalid && keys_sorted != gb->slot_of_row) c.L.disown(keys_sorted);  // the sorted slots were only needed for the group offsets
+  return seal_full(c, vs, c.vvalid ? keys_sorted : nullptr, ss, gb->gid_of_occ, nullptr, sort_desc, skew);
+}
+
+// 4-byte LSD on skewed keys: the fused kernel is skipped (a run longer than 2^19 rows): finish the sort with the one pass that is left
+static int finish_partial_lsd(const LayoutCtx& c, const SortedRuns& r) {
+  GroupedLayout& L = c.L;
+  const int64_t n = c.gb->n;
+  L.disown(r.run_start);
+  uint32_t* k2 = L.own<uint32_t>((size_t)n);
+  uint64_t* v2 = L.own<uint64_t>((size_t)n);
+  if (!k2 || !v2) return PDX_OOM;
+  const uint32_t* ks2 = nullptr;
+  const uint64_t* vs2 = nullptr;
+  PDX_TRY((radix_sort_pairs<uint64_t>(r.fkeys, r.vals, k2, v2, k2, v2, n, kFlrBits, &ks2, &vs2, true, c.s, c.st, r.low_bits)));
+  L.disown(r.fkeys);
+  L.disown(r.vals);
+  return finish_sorted_slots(c, ks2, vs2, r.sort_desc + "+finish", true);
+}
+
+// one group: the rows are grouped as they stand (no sort); null flags, if any, still go into a key per row
+static int layout_single_group(const LayoutCtx& c) {
+  pdx_groupby* gb = c.gb;
+  const uint32_t* keys = gb->slot_of_row;
+  if (c.vvalid) {
+    uint32_t* fk1 = c.L.own<uint32_t>((size_t)gb->n);
+    if (!fk1) return PDX_OOM;
+    hipLaunchKernelGGL(k_flag_keys, dim3(grid_for(gb->n, 256, 4)), dim3(256), 0, c.st, gb->slot_of_row, c.vvalid, c.values->offset, gb->n, fk1);
+    keys = fk1;
+  }
+  return finish_sorted_slots(c, keys, c.vin, "none", false);
+}
+
+// full form: stable sort of (slot, value) by slot, each group's values contiguous in row order
+static int layout_full_sort(const LayoutCtx& c) {
+  GroupedLayout& L = c.L;
+  const uint32_t* keys_sorted = nullptr;
+  const uint64_t* vs = nullptr;
+  const size_t mark = L.owned.size();  // (a bound layout's older fused form lies below the mark)
+  PDX_TRY(sort_values_by_slot(c.gb, c.vin, c.vvalid, c.values->offset, [&](size_t bytes) { return (void*)L.own<uint8_t>(bytes); }, c.s, c.st, &keys_sorted, &vs));
+  keep_only(L, mark, {keys_sorted, vs});
+  return finish_sorted_slots(c, keys_sorted, vs, "lsd", false);
+}
+
 // Stage 1 of pdx_groupby_agg for one column.  allow_fused: the request can be served by the fused last-digit kernels (the five
 // standard kinds, variance, stddev); the layout then stops LOW of the top 6 slot bits when the handle qualifies (L.fused), unless a
 // run turns out longer than kFlrMaxRun (skewed keys), in which case the sort is finished here (L.full).  Otherwise a full sort.
 static int build_layout(pdx_groupby* gb, const pdx_column* values, bool allow_fused, const AggTuning& t, GroupedLayout& L, hipStream_t st) {
-  const int64_t n = gb->n, G = gb->G;
-  const uint8_t* vvalid = validity_or_null(values);
   L.values = values->values;
-  L.validity = vvalid;
+  L.validity = validity_or_null(values);
   L.offset = values->offset;
   L.dtype = values->dtype;
   L.stream = st;
-  const std::string slots = std::string("slots=") + slots_name(gb);
-  if (gb->mode != 0) {  // segments: the rows are grouped as they stand
-    L.full = true;
-    L.vals_sorted = static_cast<const uint64_t*>(values->values) + values->offset;
-    L.seg_start = gb->seg_start;
-    L.row_valid = vvalid;
-    L.plan_full = slots + " sort=none layout=full";
-    return PDX_OK;
-  }
   Scratch s;
-  const uint64_t* vin = static_cast<const uint64_t*>(values->values) + values->offset;
-  const FusedPlan fp = allow_fused && !L.fused ? plan_fused(gb, vvalid != nullptr, t) : FusedPlan{};
-  const int low_bits = fp.low_bits;
-  const uint32_t* keys_sorted = nullptr;
-  const uint64_t* vs = nullptr;
-  bool sorted_done = false;  // narrowing sort, skewed keys: full layout built in the fused branch
-  bool partial_lsd = false;  // 4-byte slots sorted by the low bits only; a skewed input finishes with one more pass
-  std::string sort_desc;
-  if (fp.flr) {
-    const int64_t nruns = (int64_t)1 << low_bits;
-    uint32_t* run_start = L.own<uint32_t>((size_t)nruns + 1);
-    unsigned int* dmax = s.get<unsigned int>(3);  // longest run, runs over the limit, their rows
-    if (!run_start) return PDX_OOM;
-    PDX_SCRATCH_CHECK(s);
-    unsigned int hmax = 0, n_long = 0, rows_long = 0;
-    const unsigned int max_run = std::min(t.max_run, kFlrMaxRun);
-    // a few long runs (one key with a large share of the rows is enough to make one) are reduced from a side form, the rest by the
-    // fused kernels; many or very long ones: the whole column takes the classic path
-    auto side_ok = [&] { return t.hybrid && n_long > 0 && n_long <= (unsigned int)kMaxLongRuns && (int64_t)rows_long <= n / 4; };
-    const size_t mark = L.owned.size();
-    if (fp.narrow || fp.narrow_part) {
-      const int b0 = fp.narrow ? fp.low_plan.bits[0] : kPartBits, b1 = fp.narrow ? fp.low_plan.bits[1] : fp.mid_bits;
-      sort_desc = std::string(fp.narrow ? "narrow:" : "narrow_part:") + std::to_string(b0) + "+" + std::to_string(b1);
-      const int64_t ntiles = ceil_div(n, kSortTile), nchunks = ceil_div(ntiles, kColChunk);
-      uint16_t* k16 = fp.narrow ? s.get<uint16_t>((size_t)n) : gb->idx16_part;
-      const uint32_t* prev_off = fp.narrow ? gb->pass0_off : gb->part_off;  // (row 0 = where every first digit's rows begin in the input of pass 1)
-      uint8_t* k8 = L.own<uint8_t>((size_t)n);
-      uint64_t* nv0 = L.own<uint64_t>((size_t)n);
-      uint64_t* nv1 = L.own<uint64_t>((size_t)n);
-      uint32_t* nhist = s.get<uint32_t>((size_t)ntiles << 8);
-      uint32_t* nchunk = s.get<uint32_t>((size_t)(nchunks + 1) << 8);
-      if (!k8 || !nv0 || !nv1) return PDX_OOM;
-      PDX_SCRATCH_CHECK(s);
-      int rcn = PDX_OK;
-      if (fp.narrow_part) rcn = radix_scatter_only<kPartBits, uint64_t, uint8_t>(gb->bucket8, vin, nullptr, nv0, n, 0, false, gb->part_off, st);
-      else
-        rcn = with_digit_bits<4, 8>(b0, [&](auto b) {
-          return vvalid ? radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t, true>(gb->slot_of_row, vin, k16, nv0, n, gb->pass0_off, st, vvalid, values->offset)
-                        : radix_scatter_narrow<b(), uint64_t, uint32_t, uint16_t>(gb->slot_of_row, vin, k16, nv0, n, gb->pass0_off, st);
-        });
-      PDX_TRY(rcn);
-      // pass 1 in two halves: its offsets first -- the run starts and the longest run (the host needs that number to choose the
-      // reducer) follow from them alone -- then the scatter, which runs while the host reads the number back
-      rcn = with_digit_bits<4, 8>(b1, [&](auto b) { return radix_offsets<b(), uint16_t>(k16, n, 0, nhist, nchunk, true, st); });
-      PDX_TRY(rcn);
-      struct EventGuard {  // the event must not outlive an early return
-        hipEvent_t ev = nullptr;
-        ~EventGuard() { if (ev) (void)hipEventDestroy(ev); }
-      } hmax_ready;
-      {
-        PDX_PROFILE("run_starts", st);
-        // (row 0 of the pass-0 offsets = where every first digit's rows begin in the input of pass 1)
-        hipLaunchKernelGGL((k_level_starts<uint16_t>), dim3(1u << b0), dim3(256), 0, st, k16, n, prev_off, (int64_t)1 << b0, b0, b1, nhist, run_start);
-        PDX_HIP(hipMemsetAsync(dmax, 0, 3 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_run_max_len, dim3(grid_for(nruns, 256)), dim3(256), 0, st, run_start, nruns, dmax, max_run);
-        PDX_LAUNCH_CHECK();
-        PDX_HIP(hipMemcpyAsync(hmax_pinned(), dmax, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        PDX_HIP(hipEventCreateWithFlags(&hmax_ready.ev, hipEventDisableTiming));
-        PDX_HIP(hipEventRecord(hmax_ready.ev, st));
-      }
-      rcn = with_digit_bits<4, 8>(b1, [&](auto b) {
-        return vvalid ? radix_scatter_narrow<b(), uint64_t, uint16_t, uint8_t, true>(k16, nv0, k8, nv1, n, nhist, st)
-                      : radix_scatter_narrow<b(), uint64_t, uint16_t, uint8_t>(k16, nv0, k8, nv1, n, nhist, st);
-      });
-      PDX_TRY(rcn);
-      {
-        const hipError_t ew = hipEventSynchronize(hmax_ready.ev);
-        if (ew != hipSuccess) return hip_fail(ew, "pdx_groupby_agg");
-        hmax = hmax_pinned()[0];
-        n_long = hmax_pinned()[1];
-        rows_long = hmax_pinned()[2];
-      }
-      if (hmax > max_run && side_ok()) {
-        PDX_TRY((build_side<uint8_t>(gb, L, k8, nv1, run_start, nruns, low_bits, max_run, (int)n_long, (int64_t)rows_long, vvalid != nullptr, s, st)));
-        L.fused = true;
-        L.keys8 = k8;
-        L.fvals = nv1;
-        L.disown(nv0);
-      } else if (hmax > max_run) {
-        // skewed keys: the fused kernel is skipped.  Finish the sort with the one pass that is left (on the byte digits) and take the
-        // group offsets from its scatter offsets: one more level of k_level_starts gives the start of every slot's rows
-        uint32_t* ss_narrow = L.own<uint32_t>((size_t)G + 1);
-        uint32_t* slot_start = s.get<uint32_t>(((size_t)nruns << kFlrBits) + 1);
-        if (!ss_narrow) return PDX_OOM;
-        PDX_SCRATCH_CHECK(s);
-        PDX_TRY((radix_offsets<kFlrBits, uint8_t>(k8, n, 0, nhist, nchunk, true, st)));
-        const uint32_t* fkeys = nullptr;
-        if (vvalid) {  // the classic nullable reducers read the null flag from bit 31 of a 4-byte key per grouped row: write flags only
-          uint32_t* fk = L.own<uint32_t>((size_t)n);
-          if (!fk) return PDX_OOM;
-          PDX_TRY((radix_scatter_narrow<kFlrBits, uint64_t, uint8_t, uint32_t, true>(k8, nv1, fk, nv0, n, nhist, st)));
-          fkeys = fk;
-        } else {
-          PDX_TRY((radix_scatter_narrow<kFlrBits, uint64_t, uint8_t, uint8_t>(k8, nv1, (uint8_t*)nullptr, nv0, n, nhist, st)));
-        }
-        {
-          PDX_PROFILE("seg_starts", st);
-          hipLaunchKernelGGL((k_level_starts<uint8_t>), dim3((unsigned)std::min<int64_t>(nruns, 65536)), dim3(256), 0, st, k8, n, run_start, nruns, low_bits,
-                             kFlrBits, nhist, slot_start);
-          hipLaunchKernelGGL(k_seg_starts_from_slots, dim3(grid_for(G + 1, 256)), dim3(256), 0, st, slot_start, n, gb->occ_slot, G, ss_narrow);
-        }
-        PDX_LAUNCH_CHECK();
-        L.full = true;
-        L.vals_sorted = nv0;
-        L.flag_keys = fkeys;
-        L.seg_start = ss_narrow;
-        L.out_index = gb->gid_of_occ;
-        sorted_done = true;
-        keep_only(L, mark, {nv0, ss_narrow, fkeys});
-        L.disown(run_start);
-      } else {
-        L.fused = true;
-        L.keys8 = k8;
-        L.fvals = nv1;
-        L.disown(nv0);
-      }
-    } else {
-      sort_desc = "lsd:skip" + std::to_string(gb->slot_bits - low_bits);
-      PDX_TRY(sort_values_by_slot(gb, vin, vvalid, values->offset, [&](size_t bytes) { return (void*)L.own<uint8_t>(bytes); }, s, st, &keys_sorted, &vs,
-                                  gb->slot_bits - low_bits));
-      keep_only(L, mark, {keys_sorted, vs});
-      {
-        PDX_PROFILE("run_starts", st);
-        PDX_HIP(hipMemsetAsync(dmax, 0, 3 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_run_starts, dim3(grid_for(nruns + 1, 256)), dim3(256), 0, st, keys_sorted, n, low_bits, nruns, run_start, dmax);
-        hipLaunchKernelGGL(k_run_max_len, dim3(grid_for(nruns, 256)), dim3(256), 0, st, run_start, nruns, dmax, max_run);
-        PDX_LAUNCH_CHECK();
-        unsigned int h3[3] = {0, 0, 0};
-        PDX_HIP(hipMemcpyAsync(h3, dmax, sizeof(h3), hipMemcpyDeviceToHost, st));
-        PDX_HIP(hipStreamSynchronize(st));
-        hmax = h3[0];
-        n_long = h3[1];
-        rows_long = h3[2];
-      }
-      if (hmax > max_run && side_ok())
-        PDX_TRY((build_side<uint32_t>(gb, L, keys_sorted, vs, run_start, nruns, low_bits, max_run, (int)n_long, (int64_t)rows_long, vvalid != nullptr, s, st)));
-      if (hmax <= max_run || L.side_rows) {
-        L.fused = true;
-        L.fkeys = keys_sorted;
-        L.fvals = vs;
-      } else {
-        partial_lsd = true;
-        L.disown(run_start);
-      }
-    }
-    if (L.fused) {
-      L.low_bits = low_bits;
-      L.nruns = nruns;
-      L.hmax = std::min(hmax, max_run);  // (rows of the longest run the fused kernels walk)
-      L.max_run = max_run;
-      L.run_start = run_start;
-      L.plan_fused = slots + " sort=" + sort_desc + " layout=fused" + (L.side_rows ? " side=" + std::to_string(L.side_runs) : std::string());
-      return PDX_OK;
-    }
-  }
-  // ---- full form: stable sort of (slot, value) by slot, each group's values contiguous in row order
-  if (!sorted_done) {
-    const size_t mark = L.owned.size();
-    if (partial_lsd) {
-      // the fused kernel was skipped (a run longer than 2^19 rows: skewed keys): finish the sort with the one pass that is left
-      uint32_t* k2 = L.own<uint32_t>((size_t)n);
-      uint64_t* v2 = L.own<uint64_t>((size_t)n);
-      if (!k2 || !v2) return PDX_OOM;
-      const uint32_t* ks2 = nullptr;
-      const uint64_t* vs2 = nullptr;
-      PDX_TRY((radix_sort_pairs<uint64_t>(keys_sorted, vs, k2, v2, k2, v2, n, kFlrBits, &ks2, &vs2, true, s, st, low_bits)));
-      L.disown(keys_sorted);
-      L.disown(vs);
-      keys_sorted = ks2;
-      vs = vs2;
-      sort_desc += "+finish";
-    } else if (G == 1 && gb->slot_of_row) {
-      // one group: the rows are grouped as they stand (no sort); null flags, if any, still go into a key per row
-      keys_sorted = gb->slot_of_row;
-      if (vvalid) {
-        uint32_t* fk1 = L.own<uint32_t>((size_t)n);
-        if (!fk1) return PDX_OOM;
-        hipLaunchKernelGGL(k_flag_keys, dim3(grid_for(n, 256, 4)), dim3(256), 0, st, gb->slot_of_row, vvalid, values->offset, n, fk1);
-        keys_sorted = fk1;
-      }
-      vs = vin;
-      sort_desc = "none";
-    } else {
-      PDX_TRY(sort_values_by_slot(gb, vin, vvalid, values->offset, [&](size_t bytes) { return (void*)L.own<uint8_t>(bytes); }, s, st, &keys_sorted, &vs));
-      keep_only(L, mark, {keys_sorted, vs});
-      sort_desc = "lsd";
-    }
-    uint32_t* ss = L.own<uint32_t>((size_t)G + 1);
-    if (!ss) return PDX_OOM;
-    {
-      PDX_PROFILE("seg_starts", st);
-      hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(G + 1, 256)), dim3(256), 0, st, keys_sorted, n, gb->occ_slot, G, ss);
-    }
-    PDX_LAUNCH_CHECK();
-    L.full = true;
-    L.vals_sorted = vs;
-    L.flag_keys = vvalid ? keys_sorted : nullptr;
-    if (!vvalid && keys_sorted != gb->slot_of_row) L.disown(keys_sorted);  // the sorted slots were only needed for the group offsets
-    L.seg_start = ss;
-    L.out_index = gb->gid_of_occ;
-  }
-  L.plan_full = slots + " sort=" + sort_desc + " layout=full" + (fp.flr ? " skew=1" : "");
-  return PDX_OK;
+  const LayoutCtx c{gb, values, validity_or_null(values), static_cast<const uint64_t*>(values->values) + values->offset, t, L, s, st};
+  if (gb->mode != 0) return layout_segments(c);
+  const FusedPlan fp = allow_fused && !L.fused ? plan_fused(gb, c.vvalid != nullptr, t) : FusedPlan{};
+  if (!fp.flr) return gb->G == 1 && gb->slot_of_row ? layout_single_group(c) : layout_full_sort(c);
+  SortedRuns r;
+  const bool narrow = fp.narrow || fp.narrow_part;
+  PDX_TRY(narrow ? sort_narrow_to_runs(c, fp, &r) : sort_lsd_to_runs(c, fp, &r));
+  if (r.stats.hmax <= r.max_run) return seal_fused(c, r, SideForm{});
+  if (!r.stats.side_ok(t, gb->n)) return narrow ? finish_narrow_skewed(c, r) : finish_partial_lsd(c, r);
+  SideForm side;
+  PDX_TRY(narrow ? build_side(c, r, r.keys8, &side) : build_side(c, r, r.fkeys, &side));
+  return seal_fused(c, r, side);
 }

@@ -26,9 +26,11 @@
 //      Dense slots + values without nulls: narrowing sort (the key shrinks 4 -> 2 -> 1 byte as digits are consumed; run and
 //      group starts come from the scatter offsets, k_level_starts).  Runs longer than 2^19 rows (hot keys) are skipped by the
 //      fused kernels and reduced from a side form of the layout (build_side, gb_layout.hpp).
+//      Host side: gb_layout.hpp, build_layout over one function per path, each ending in seal_fused / seal_full.
 //   4. classic reducers on fully sorted values (skewed keys, small inputs, resample, product/first/last): k_seg_reduce (one wave
 //      per group, 16-value leaves + shuffle tree + counter), k_seg_reduce_mid (batches of short groups per wave),
 //      k_seg_reduce_sub + k_seg_combine_big (many waves per long group), k_seg_reduce_nullable.
+//      Host side of 3. and 4.: gb_agg.hpp, one function per stage of pdx_groupby_agg.
 // All fp64 sums reproduce Arrow's pairwise summation bit for bit.  Algorithmic bytes: 16 B/row (8 key + 8 value).
 #include <stdlib.h>
 #include <string.h>
@@ -430,142 +432,10 @@ int pdx_groupby_sizes(pdx_groupby* gb, int64_t* out_sizes, void* stream) {
   return PDX_OK;
 }
 
-// ---------------------------------------------------------------- stage 2 of pdx_groupby_agg: reducers over a GroupedLayout
 }  // extern "C"
 
+// ---------------------------------------------------------------- bound columns: layouts (and cached results) kept in the handle
 namespace pdx {
-struct AggRequest {
-  SegOut o{};
-  bool want_pw = false, want_mm = false, want_is = false, want_std5 = false;
-  // the "next" kinds (variance, stddev, product, first, last) run after the five standard ones on the same grouped values
-  double *var_out = nullptr, *std_out = nullptr;
-  void *prod_out = nullptr, *first_out = nullptr, *last_out = nullptr;
-  bool is_f = true;
-  bool std_only() const { return (want_std5 || var_out || std_out) && !prod_out && !first_out && !last_out; }  // (variance: two more fused passes)
-};
-
-// one segmented reduce of `vals` (float64 or int64 per f64) over `G` segments of `nrows` grouped rows into `oo`; nullable: the null flag of
-// every grouped row is bit 31 of flag_keys (or read in place from row_valid, segments mode); ok_bytes: 1 = the group has a valid value
-static int reduce_segments(bool nullable, const uint32_t* flag_keys, const uint8_t* row_valid, int64_t valid_off, const uint32_t* seg_start, int64_t G,
-                           int64_t nrows, const void* vals, bool f64, const SegOut& oo, bool pw, bool mm, bool is, const uint32_t* oidx, uint8_t* ok_bytes,
-                           Scratch& s, hipStream_t st) {
-  PDX_PROFILE("seg_reduce", st);
-  const int64_t n = nrows;
-  if (!nullable) {
-    if (f64) return launch_seg_reduce_dense<double>(static_cast<const double*>(vals), seg_start, G, oidx, oo, pw, mm, is, n, s, st);
-    return launch_seg_reduce_dense<long long>(static_cast<const long long*>(vals), seg_start, G, oidx, oo, pw, mm, is, n, s, st);
-  }
-  const int grid = (int)std::min<int64_t>(ceil_div(G, kSegWaves), (int64_t)kCUs * 8);
-  if (f64)
-    hipLaunchKernelGGL((k_seg_reduce_nullable<double>), dim3(grid), dim3(kSegWaves * 64), 0, st, static_cast<const double*>(vals), flag_keys, row_valid,
-                       valid_off, seg_start, G, oidx, oo, ok_bytes);
-  else
-    hipLaunchKernelGGL((k_seg_reduce_nullable<long long>), dim3(grid), dim3(kSegWaves * 64), 0, st, static_cast<const long long*>(vals), flag_keys,
-                       row_valid, valid_off, seg_start, G, oidx, oo, ok_bytes);
-  PDX_LAUNCH_CHECK();
-  return reduce_huge_nullable_groups(vals, f64 ? PDX_FLOAT64 : PDX_INT64, flag_keys, row_valid, valid_off, seg_start, G, oidx, n, oo, ok_bytes, s, st);
-}
-// ... over a full layout; vals == the layout's own values or an array in the same order
-static int reduce_full(const pdx_groupby* gb, const GroupedLayout& L, const void* vals, bool f64, const SegOut& oo, bool pw, bool mm, bool is,
-                       const uint32_t* oidx, uint8_t* ok_bytes, Scratch& s, hipStream_t st) {
-  return reduce_segments(L.validity != nullptr, L.flag_keys, L.row_valid, L.offset, L.seg_start, gb->G, gb->n, vals, f64, oo, pw, mm, is, oidx, ok_bytes, s, st);
-}
-// ... over the side form of a fused layout (the rows of its long runs): EVERY group's outputs are written -- zeros / nulls for the groups
-// outside the long runs -- so it runs before the fused kernel, which then writes the groups of the runs it walks
-static int reduce_side(const pdx_groupby* gb, const GroupedLayout& L, const SegOut& oo, bool pw, bool mm, bool is, uint8_t* ok_bytes, const double* sqmean,
-                       Scratch& s, hipStream_t st) {
-  const bool is_f = L.dtype == PDX_FLOAT64, nullable = L.validity != nullptr;
-  const void* vals = L.side_vals;
-  bool f64 = is_f;
-  if (sqmean) {  // second pass of variance: (x - mean of x's group)^2, summed over the same valid runs
-    double* d = s.get<double>((size_t)L.side_rows);
-    PDX_SCRATCH_CHECK(s);
-    PDX_PROFILE("seg_sqdev", st);
-    const int grid = (int)std::min<int64_t>(ceil_div(gb->G, 4), (int64_t)kCUs * 16);
-    if (is_f) hipLaunchKernelGGL((k_seg_sqdev<double>), dim3(grid), dim3(256), 0, st, reinterpret_cast<const double*>(L.side_vals), L.side_seg, gb->G, sqmean, d, gb->gid_of_occ);
-    else hipLaunchKernelGGL((k_seg_sqdev<long long>), dim3(grid), dim3(256), 0, st, reinterpret_cast<const long long*>(L.side_vals), L.side_seg, gb->G, sqmean, d, gb->gid_of_occ);
-    PDX_LAUNCH_CHECK();
-    vals = d;
-    f64 = true;
-  }
-  return reduce_segments(nullable, L.side_keys, nullptr, 0, L.side_seg, gb->G, L.side_rows, vals, f64, oo, pw, mm, is, gb->gid_of_occ, ok_bytes, s, st);
-}
-
-// The fused last digit: rank by the top 6 slot bits + Arrow's leaf / counter recurrence in one pass over a fused layout.
-// ok_bytes (nullable values): 1 = the group has a valid value; sqmean: second pass of variance.
-static int reduce_fused(const pdx_groupby* gb, const GroupedLayout& L, const AggTuning& t, const SegOut& oo, bool pw, bool mm, bool is, uint8_t* okbytes,
-                        const double* sqmean, Scratch& s, hipStream_t st, std::string* reducer) {
-  if (L.side_rows) PDX_TRY(reduce_side(gb, L, oo, pw, mm, is, okbytes, sqmean, s, st));
-  const unsigned int max_run = L.max_run ? L.max_run : 0xFFFFFFFFu;
-  PDX_PROFILE("fused_last_digit_reduce", st);
-  const bool nullable = L.validity != nullptr, is_f = L.dtype == PDX_FLOAT64;
-  const int64_t nruns = L.nruns, n = gb->n;
-  const int low_bits = L.low_bits;
-  const uint8_t* keys8 = L.keys8;
-  const uint32_t* keys_sorted = L.fkeys;
-  const uint64_t* vs = L.fvals;
-  const uint32_t* run_start = L.run_start;
-  const int grid = (int)std::min<int64_t>(nruns, (int64_t)kCUs * t.flr_wgs_per_cu);
-  const bool dense = pw && !mm && !is && !nullable;
-  // (values with nulls, sum / mean / count: the thread-per-leaf form is opt-in, PDX_FLR_NULL_PW=1 -- measured 11.3 ms against
-  //  10.7 ms of the literal per-lane replay at 5 % nulls: its per-group walk over the leaf markers is as serial as the replay)
-  const bool nullpw = pw && !mm && !is && nullable && t.null_pw;
-#define FLR_LAUNCH(TT, DD)                                                                                                                       \
-  if (keys8 && nullpw)                                                                                                                           \
-    hipLaunchKernelGGL((k_flr_reduce<TT, false, uint8_t, true>), dim3(grid), dim3(kSortBlock), 0, st, keys8, reinterpret_cast<const TT*>(vs), run_start, \
-                       nruns, low_bits, gb->gid_of_slot, oo, okbytes, (int)pw, (int)mm, (int)is, 1, sqmean, max_run);                              \
-  else if (nullpw)                                                                                                                               \
-    hipLaunchKernelGGL((k_flr_reduce<TT, false, uint32_t, true>), dim3(grid), dim3(kSortBlock), 0, st, keys_sorted, reinterpret_cast<const TT*>(vs),   \
-                       run_start, nruns, low_bits, gb->gid_of_slot, oo, okbytes, (int)pw, (int)mm, (int)is, 1, sqmean, max_run);                   \
-  else if (keys8)                                                                                                                                \
-    hipLaunchKernelGGL((k_flr_reduce<TT, DD, uint8_t>), dim3(grid), dim3(kSortBlock), 0, st, keys8, reinterpret_cast<const TT*>(vs), run_start, nruns, \
-                       low_bits, gb->gid_of_slot, oo, okbytes, (int)pw, (int)mm, (int)is, nullable ? 1 : 0, sqmean, max_run);                      \
-  else                                                                                                                                           \
-    hipLaunchKernelGGL((k_flr_reduce<TT, DD>), dim3(grid), dim3(kSortBlock), 0, st, keys_sorted, reinterpret_cast<const TT*>(vs), run_start, nruns, \
-                       low_bits, gb->gid_of_slot, oo, okbytes, (int)pw, (int)mm, (int)is, nullable ? 1 : 0, sqmean, max_run)
-  // one WAVE per run (flr_wave.hpp) for everything but the dense sum / mean / count: nullable values, min / max and int64 sums
-  // were a per-lane replay by wave 0 alone in the workgroup-per-run kernel (5 % nulls: 10.7 -> 4.9 ms per 1e9 rows); the dense
-  // fast path of k_flr_reduce (thread per leaf) is still ahead of the wave form (3.0 vs 3.3 ms).  PDX_FLR_WAVE=1 / 0 force either.
-  const bool wave_form = !nullpw && (t.wave_force >= 0 ? t.wave_force != 0 : !dense);
-  if (reducer) *reducer = wave_form ? "flr_wave" : (nullpw ? "flr_reduce_nullpw" : (dense ? "flr_reduce_dense" : "flr_reduce"));
-  if (wave_form) {
-    const int wgrid = (int)std::min<int64_t>(nruns, (int64_t)kCUs * t.fw_wgs_per_cu);
-    const bool pw_only = pw && !mm && !is;
-    // counter levels: a group cannot outgrow its run, and a leaf holds 16 rows unless nulls cut it short
-    const uint64_t max_leaves = nullable ? (uint64_t)L.hmax + 1 : (uint64_t)L.hmax / 16 + 2;
-    const int fw_levels = std::max(2, ilog2(max_leaves + 1));  // 2^levels > leaves: level index <= levels - 1
-    const size_t fw_lds = (size_t)fw_lds_bytes(nullable, fw_levels);
-#define FW_LAUNCH(TT, KK, KPTR, NN, PP)                                                                                                  \
-  hipLaunchKernelGGL((k_flr_wave<TT, KK, NN, PP>), dim3(wgrid), dim3(64), fw_lds, st, KPTR, reinterpret_cast<const TT*>(vs), n, run_start, nruns, low_bits, \
-                     gb->gid_of_slot, oo, okbytes, (int)pw, (int)mm, (int)is, sqmean, fw_levels, max_run)
-#define FW_DISPATCH(TT)                                                                        \
-  if (keys8) {                                                                                 \
-    if (nullable) { if (pw_only) FW_LAUNCH(TT, uint8_t, keys8, true, true); else FW_LAUNCH(TT, uint8_t, keys8, true, false); }          \
-    else { if (pw_only) FW_LAUNCH(TT, uint8_t, keys8, false, true); else FW_LAUNCH(TT, uint8_t, keys8, false, false); }              \
-  } else {                                                                                     \
-    if (nullable) { if (pw_only) FW_LAUNCH(TT, uint32_t, keys_sorted, true, true); else FW_LAUNCH(TT, uint32_t, keys_sorted, true, false); } \
-    else { if (pw_only) FW_LAUNCH(TT, uint32_t, keys_sorted, false, true); else FW_LAUNCH(TT, uint32_t, keys_sorted, false, false); } \
-  }
-    if (is_f) { FW_DISPATCH(double) } else { FW_DISPATCH(long long) }
-#undef FW_DISPATCH
-#undef FW_LAUNCH
-  } else if (is_f) {
-    if (dense) { FLR_LAUNCH(double, true); }
-    else { FLR_LAUNCH(double, false); }
-  } else {
-    if (dense) { FLR_LAUNCH(long long, true); }
-    else { FLR_LAUNCH(long long, false); }
-  }
-#undef FLR_LAUNCH
-  PDX_LAUNCH_CHECK();
-  return PDX_OK;
-}
-
-__global__ void k_mean_from_cache(const double* __restrict__ sum, const long long* __restrict__ cnt, int64_t G, double* __restrict__ out) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < G; i += stride) out[i] = cnt[i] ? pw_mean(sum[i], (double)cnt[i]) : 0.0;
-}
-
 static GroupedLayout* find_bound(pdx_groupby* gb, const pdx_column* values) {
   const void* vv = validity_or_null(values);
   for (auto& b : gb->bound)
@@ -600,6 +470,8 @@ static void enforce_bind_limit(pdx_groupby* gb, const GroupedLayout* keep) {
     gb->bound.erase(gb->bound.begin() + (long)victim);
   }
 }
+
+#include "gb_agg.hpp"
 }  // namespace pdx
 
 extern "C" {
@@ -662,6 +534,8 @@ int pdx_groupby_last_plan(const pdx_groupby* gb, char* buf, size_t buf_len) {
   return PDX_OK;
 }
 
+// Stage 1: the grouped layout of the value column (build_layout, gb_layout.hpp; a bound column brings its own); stage 2: the reducers
+// over it (gb_agg.hpp).  Outputs are valid on return.
 int pdx_groupby_agg(pdx_groupby* gb, const pdx_column* values, const int* kinds, int nk, pdx_mut_column* outs, void* stream) {
   if (!gb || !kinds || !outs || nk <= 0) return fail(PDX_INVALID, "pdx_groupby_agg: null argument");
   PDX_TRY(check_column(values, "pdx_groupby_agg"));
@@ -671,224 +545,25 @@ int pdx_groupby_agg(pdx_groupby* gb, const pdx_column* values, const int* kinds,
   bool extra = values->dtype == PDX_BOOL;
   for (int k = 0; k < nk; ++k) extra = extra || kinds[k] == PDX_AGG_ALL || kinds[k] == PDX_AGG_ANY || kinds[k] == PDX_AGG_COUNT_DISTINCT;
   if (extra) return groupby_agg_extra(gb, values, kinds, nk, outs, stream);
-  const bool is_f = values->dtype == PDX_FLOAT64;
-  if (!is_f && values->dtype != PDX_INT64) return fail(PDX_NOT_IMPLEMENTED, "pdx_groupby_agg: values must be int64 or float64");
+  if (values->dtype != PDX_FLOAT64 && values->dtype != PDX_INT64) return fail(PDX_NOT_IMPLEMENTED, "pdx_groupby_agg: values must be int64 or float64");
   hipStream_t st = as_stream(stream);
   gb->use_on(st);  // ordered behind the handle's creation; frees of its blocks are ordered behind this stream
-  const int64_t n = gb->n, G = gb->G;
-  const uint8_t* vvalid = validity_or_null(values);
   AggRequest rq;
-  rq.is_f = is_f;
-  SegOut& o = rq.o;
-  for (int k = 0; k < nk; ++k) {
-    pdx_mut_column* oc = &outs[k];
-    if (oc->length < G) return fail(PDX_INVALID, "pdx_groupby_agg: output too small");
-    if (G && !oc->values) return fail(PDX_INVALID, "pdx_groupby_agg: null output buffer");
-    int want_dt;
-    bool needs_validity = vvalid != nullptr;
-    switch (kinds[k]) {
-      case PDX_AGG_SUM:
-        want_dt = is_f ? PDX_FLOAT64 : PDX_INT64;
-        if (is_f) { o.sum_f = static_cast<double*>(oc->values); rq.want_pw = true; }
-        else { o.sum_i = static_cast<long long*>(oc->values); rq.want_is = true; }
-        rq.want_std5 = true;
-        break;
-      case PDX_AGG_MEAN: want_dt = PDX_FLOAT64; o.mean = static_cast<double*>(oc->values); rq.want_pw = true; rq.want_std5 = true; break;
-      case PDX_AGG_MIN: want_dt = values->dtype; o.vmin = oc->values; rq.want_mm = true; rq.want_std5 = true; break;
-      case PDX_AGG_MAX: want_dt = values->dtype; o.vmax = oc->values; rq.want_mm = true; rq.want_std5 = true; break;
-      case PDX_AGG_COUNT: want_dt = PDX_INT64; o.count = static_cast<long long*>(oc->values); needs_validity = false; rq.want_std5 = true; break;
-      case PDX_AGG_VARIANCE: want_dt = PDX_FLOAT64; rq.var_out = static_cast<double*>(oc->values); break;
-      case PDX_AGG_STDDEV: want_dt = PDX_FLOAT64; rq.std_out = static_cast<double*>(oc->values); break;
-      case PDX_AGG_PRODUCT: want_dt = values->dtype; rq.prod_out = oc->values; break;
-      case PDX_AGG_FIRST: want_dt = values->dtype; rq.first_out = oc->values; break;
-      case PDX_AGG_LAST: want_dt = values->dtype; rq.last_out = oc->values; break;
-      default: return fail(PDX_INVALID, "pdx_groupby_agg: unknown aggregate kind");
-    }
-    if (oc->dtype != want_dt) return fail(PDX_INVALID, "pdx_groupby_agg: output dtype does not match the aggregate's result type");
-    if (needs_validity && !oc->validity)
-      return fail(PDX_INVALID, "pdx_groupby_agg: values carry nulls but an output has no validity buffer");
-    oc->length = G;
-    oc->null_count = needs_validity ? -1 : 0;
-  }
-  if (G == 0) return PDX_OK;
+  PDX_TRY(parse_agg_request(gb, values, kinds, nk, outs, &rq));
+  if (gb->G == 0) return PDX_OK;
   const AggTuning t = AggTuning::read();
-  // ---- stage 1: the grouped layout (a bound column brings its own)
-  GroupedLayout local;
-  GroupedLayout* Lp = find_bound(gb, values);
-  const bool bound = Lp != nullptr;
-  if (!Lp) Lp = &local;
-  GroupedLayout& L = *Lp;
-  const bool std_only = rq.std_only();
-  const size_t bytes_before = L.bytes;
-  // count / min / max / int64 sum do not depend on the order of a group's rows: when nothing else is asked for and no sorted layout of
-  // the column exists yet, they skip the value sort (gb_acc.hpp: one partition pass + accumulators in LDS)
   const AccTuning at = AccTuning::read();
-  const bool order_free = rq.want_std5 && !rq.want_pw && !rq.var_out && !rq.std_out && !rq.prod_out && !rq.first_out && !rq.last_out;
-  AccGeom ag;
-  // (a BOUND column's int64 sum keeps the sorted layout: gb.sum(c) is usually followed by gb.mean(c), which needs it -- Arrow's int64 mean
-  //  is the pairwise sum of the doubles -- and the layout then serves both; min / max / count of a bound column do skip the sort)
-  if (order_free && !(bound && rq.want_is) && !L.fused && !L.full)
-    ag = acc_geometry(gb, vvalid != nullptr, (o.vmin ? kAccMin : 0u) | (o.vmax ? kAccMax : 0u) | (o.sum_i ? kAccSum : 0u) | (o.count ? kAccCnt : 0u), is_f, at);
-  const bool use_acc = ag.ok;
-  if (!use_acc && ((!L.fused && !L.full) || (!std_only && !L.full))) PDX_TRY(build_layout(gb, values, std_only, t, L, st));
-  const bool use_fused = std_only && L.fused;
-  Scratch s;
-  std::string reducer, acc_plan;
-  auto pack_validity = [&](uint8_t* bits, const uint8_t* ok_bytes) {
-    if (!bits) return;
-    if (!ok_bytes) hipMemsetAsync(bits, 0xFF, (size_t)((G + 7) / 8), st);
-    else hipLaunchKernelGGL(k_pack_bytes, dim3(grid_for((G + 7) / 8, 256)), dim3(256), 0, st, ok_bytes, G, bits);
-  };
-  // the five standard kinds from one reduce into `oo`
-  auto reduce_std = [&](const SegOut& oo, bool pw, bool mm, bool is, uint8_t* okb) -> int {
-    if (use_acc) {
-      reducer = "lds_acc";
-      return reduce_acc(gb, ag, values, oo, okb, at, s, st, &acc_plan);
-    }
-    if (use_fused) return reduce_fused(gb, L, t, oo, pw, mm, is, okb, nullptr, s, st, &reducer);
-    reducer = vvalid ? "seg_reduce_nullable" : "seg_reduce";
-    return reduce_full(gb, L, L.vals_sorted, is_f, oo, pw, mm, is, L.out_index, okb, s, st);
-  };
-  std::string cache_note;
-  if (rq.want_std5 && bound) {
-    // a bound column keeps its per-group sum / count (/ min / max): sum(); mean(); count() as three calls cost one reduce
-    const bool have_cnt = L.have_pw || L.have_count, have_isum = L.have_pw || L.have_is;
-    const bool need_sumfam = (rq.want_pw && !L.have_pw) || (rq.want_is && !have_isum) || (o.count && !have_cnt), need_mm = rq.want_mm && !L.have_mm;
-    if (use_acc && (need_sumfam || need_mm)) {
-      // order-free kinds of a bound column: only what is asked for is computed and kept
-      const bool need_is = rq.want_is && !have_isum, need_cnt = o.count && !have_cnt;
-      if (need_cnt && !L.c_count) L.c_count = L.own<long long>((size_t)G);
-      if (vvalid && !L.c_ok) L.c_ok = L.own<uint8_t>((size_t)G);
-      if (need_is && !L.c_isum) L.c_isum = L.own<long long>((size_t)G);
-      if (need_mm && !L.c_min) {
-        L.c_min = L.own<uint64_t>((size_t)G);
-        L.c_max = L.own<uint64_t>((size_t)G);
-      }
-      if ((need_cnt && !L.c_count) || (vvalid && !L.c_ok) || (need_is && !L.c_isum) || (need_mm && (!L.c_min || !L.c_max))) return PDX_OOM;
-      SegOut c{};
-      if (need_cnt) c.count = L.c_count;
-      if (need_is) c.sum_i = L.c_isum;
-      if (need_mm) {
-        c.vmin = L.c_min;
-        c.vmax = L.c_max;
-      }
-      PDX_TRY(reduce_std(c, false, need_mm, need_is, L.c_ok));
-      L.have_count = L.have_count || need_cnt;
-      L.have_is = L.have_is || need_is;
-      L.have_mm = L.have_mm || need_mm;
-      cache_note = " cache=fill";
-    } else if (need_sumfam || need_mm) {
-      if (!L.c_count) L.c_count = L.own<long long>((size_t)G);
-      if (vvalid && !L.c_ok) L.c_ok = L.own<uint8_t>((size_t)G);
-      if (need_sumfam && !L.c_sum) L.c_sum = L.own<double>((size_t)G);
-      if (need_sumfam && !is_f && !L.c_isum) L.c_isum = L.own<long long>((size_t)G);
-      if (need_mm && !L.c_min) {
-        L.c_min = L.own<uint64_t>((size_t)G);
-        L.c_max = L.own<uint64_t>((size_t)G);
-      }
-      if (!L.c_count || (vvalid && !L.c_ok) || (need_sumfam && (!L.c_sum || (!is_f && !L.c_isum))) || (need_mm && (!L.c_min || !L.c_max))) return PDX_OOM;
-      SegOut c{};
-      c.count = L.c_count;
-      if (need_sumfam) {
-        c.sum_f = L.c_sum;
-        if (!is_f) c.sum_i = L.c_isum;
-      }
-      if (need_mm) {
-        c.vmin = L.c_min;
-        c.vmax = L.c_max;
-      }
-      PDX_TRY(reduce_std(c, need_sumfam, need_mm, need_sumfam && !is_f, L.c_ok));
-      L.have_pw = L.have_pw || need_sumfam;
-      L.have_mm = L.have_mm || need_mm;
-      cache_note = " cache=fill";
-    } else {
-      cache_note = " cache=hit";
-      reducer = "none";
-    }
-    const size_t gb8 = (size_t)G * 8;
-    if (o.sum_f) PDX_HIP(hipMemcpyAsync(o.sum_f, L.c_sum, gb8, hipMemcpyDeviceToDevice, st));
-    if (o.sum_i) PDX_HIP(hipMemcpyAsync(o.sum_i, L.c_isum, gb8, hipMemcpyDeviceToDevice, st));
-    if (o.count) PDX_HIP(hipMemcpyAsync(o.count, L.c_count, gb8, hipMemcpyDeviceToDevice, st));
-    if (o.vmin) PDX_HIP(hipMemcpyAsync(o.vmin, L.c_min, gb8, hipMemcpyDeviceToDevice, st));
-    if (o.vmax) PDX_HIP(hipMemcpyAsync(o.vmax, L.c_max, gb8, hipMemcpyDeviceToDevice, st));
-    if (o.mean) hipLaunchKernelGGL(k_mean_from_cache, dim3(grid_for(G, 256)), dim3(256), 0, st, L.c_sum, L.c_count, G, o.mean);
-    for (int k = 0; k < nk; ++k)
-      if (kinds[k] <= PDX_AGG_COUNT) pack_validity(static_cast<uint8_t*>(outs[k].validity), kinds[k] == PDX_AGG_COUNT ? nullptr : L.c_ok);
-    PDX_LAUNCH_CHECK();
-  } else if (rq.want_std5) {
-    uint8_t* okb = vvalid ? s.get<uint8_t>((size_t)G) : nullptr;
-    PDX_SCRATCH_CHECK(s);
-    PDX_TRY(reduce_std(o, rq.want_pw, rq.want_mm, rq.want_is, okb));
-    for (int k = 0; k < nk; ++k)
-      if (kinds[k] <= PDX_AGG_COUNT) pack_validity(static_cast<uint8_t*>(outs[k].validity), kinds[k] == PDX_AGG_COUNT ? nullptr : okb);
-    PDX_LAUNCH_CHECK();
-  }
-  if (rq.var_out || rq.std_out) {
-    // Arrow's two passes: mean = pairwise sum / count, then the pairwise sum of (x - mean)^2 over the same valid runs
-    double* m2 = s.get<double>((size_t)G);
-    long long* cnt_g = s.get<long long>((size_t)G);
-    uint8_t* ok2 = vvalid ? s.get<uint8_t>((size_t)G) : nullptr;
-    uint8_t* ok1 = vvalid ? s.get<uint8_t>((size_t)G) : nullptr;
-    double* mean_g = s.get<double>((size_t)G);
-    PDX_SCRATCH_CHECK(s);
-    SegOut o1{};
-    o1.mean = mean_g;
-    SegOut o2{};
-    o2.sum_f = m2;
-    o2.count = cnt_g;
-    if (use_fused) {
-      // on the same partially sorted rows: per-group mean (group-id order), then the squared deviations formed inside the kernel
-      PDX_TRY(reduce_fused(gb, L, t, o1, true, false, false, ok1, nullptr, s, st, &reducer));
-      PDX_TRY(reduce_fused(gb, L, t, o2, true, false, false, ok2, mean_g, s, st, nullptr));
-    } else {
-      if (reducer.empty()) reducer = vvalid ? "seg_reduce_nullable" : "seg_reduce";
-      double* d = s.get<double>((size_t)n);
-      PDX_SCRATCH_CHECK(s);
-      PDX_TRY(reduce_full(gb, L, L.vals_sorted, is_f, o1, true, false, false, nullptr, ok1, s, st));  // segment order
-      {
-        PDX_PROFILE("seg_sqdev", st);
-        const int grid = (int)std::min<int64_t>(ceil_div(G, 4), (int64_t)kCUs * 16);
-        if (is_f) hipLaunchKernelGGL((k_seg_sqdev<double>), dim3(grid), dim3(256), 0, st, static_cast<const double*>(L.vals_sorted), L.seg_start, G, mean_g, d);
-        else hipLaunchKernelGGL((k_seg_sqdev<long long>), dim3(grid), dim3(256), 0, st, static_cast<const long long*>(L.vals_sorted), L.seg_start, G, mean_g, d);
-        PDX_LAUNCH_CHECK();
-      }
-      PDX_TRY(reduce_full(gb, L, d, true, o2, true, false, false, L.out_index, ok2, s, st));
-    }
-    hipLaunchKernelGGL(k_var_finish, dim3(grid_for(G, 256)), dim3(256), 0, st, m2, cnt_g, G, rq.var_out, rq.std_out);
-    for (int k = 0; k < nk; ++k)
-      if (kinds[k] == PDX_AGG_VARIANCE || kinds[k] == PDX_AGG_STDDEV) pack_validity(static_cast<uint8_t*>(outs[k].validity), ok2);
-    PDX_LAUNCH_CHECK();
-  }
-  if (rq.prod_out || rq.first_out || rq.last_out) {
-    uint8_t* pok = (vvalid && rq.prod_out) ? s.get<uint8_t>((size_t)G) : nullptr;
-    uint8_t* fok = (vvalid && rq.first_out) ? s.get<uint8_t>((size_t)G) : nullptr;
-    uint8_t* lok = (vvalid && rq.last_out) ? s.get<uint8_t>((size_t)G) : nullptr;
-    PDX_SCRATCH_CHECK(s);
-    {
-      PDX_PROFILE("seg_product_first_last", st);
-      const int pf_grid = (int)std::min<int64_t>(ceil_div(G, 4), (int64_t)kCUs * 16);
-      if (is_f)
-        hipLaunchKernelGGL((k_seg_product_first_last<double>), dim3(pf_grid), dim3(256), 0, st, static_cast<const double*>(L.vals_sorted), L.flag_keys,
-                           L.row_valid, values->offset, L.seg_start, G, L.out_index, static_cast<double*>(rq.prod_out), pok, static_cast<double*>(rq.first_out),
-                           fok, static_cast<double*>(rq.last_out), lok);
-      else
-        hipLaunchKernelGGL((k_seg_product_first_last<long long>), dim3(pf_grid), dim3(256), 0, st, static_cast<const long long*>(L.vals_sorted),
-                           L.flag_keys, L.row_valid, values->offset, L.seg_start, G, L.out_index, static_cast<long long*>(rq.prod_out), pok,
-                           static_cast<long long*>(rq.first_out), fok, static_cast<long long*>(rq.last_out), lok);
-    }
-    for (int k = 0; k < nk; ++k) {
-      if (kinds[k] == PDX_AGG_PRODUCT) pack_validity(static_cast<uint8_t*>(outs[k].validity), pok);
-      if (kinds[k] == PDX_AGG_FIRST) pack_validity(static_cast<uint8_t*>(outs[k].validity), fok);
-      if (kinds[k] == PDX_AGG_LAST) pack_validity(static_cast<uint8_t*>(outs[k].validity), lok);
-    }
-    PDX_LAUNCH_CHECK();
-    if (reducer.empty() || reducer == "none") reducer = "seg_product_first_last";
-  }
-  if (use_acc)
-    gb->last_plan = (acc_plan.empty() ? std::string("slots=") + slots_name(gb) + " sort=none layout=none reducer=none" : acc_plan) + (bound ? " bound=1" : " bound=0") + cache_note;
-  else
-    gb->last_plan = (use_fused ? L.plan_fused : L.plan_full) + " reducer=" + reducer + (bound ? " bound=1" : " bound=0") + cache_note;
-  if (bound && L.bytes != bytes_before) enforce_bind_limit(gb, &L);
+  GroupedLayout local;
+  GroupedLayout* bound = find_bound(gb, values);
+  Scratch s;  // (declared after `local`: scratch goes back to the pool first)
+  AggCtx c{gb, values, validity_or_null(values), bound ? *bound : local, t, at, s, st, bound != nullptr};
+  const size_t bytes_before = c.L.bytes;
+  PDX_TRY(choose_reducer(c, rq));
+  if (rq.want_std5) PDX_TRY(c.bound ? agg_std_bound(c, rq) : agg_std_unbound(c, rq));
+  if (rq.var_out || rq.std_out) PDX_TRY(agg_variance(c, rq));
+  if (rq.prod_out || rq.first_out || rq.last_out) PDX_TRY(agg_product_first_last(c, rq));
+  gb->last_plan = compose_plan(c);
+  if (c.bound && c.L.bytes != bytes_before) enforce_bind_limit(gb, &c.L);
   PDX_HIP(hipStreamSynchronize(st));  // outputs are valid on return; scratch and a local layout go back to the pool on exit
   return PDX_OK;
 }

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from _create_plans import pinned_slots
+from _create_plans import pinned_plan, pinned_slots
 
 pytestmark = pytest.mark.gpu
 
@@ -78,6 +78,7 @@ def test_tile_boundaries_groupby_and_filter(px, n):
             assert np.array_equal(gb.unique_keys().to_numpy()[0], uniq)
             got = gb.agg(C.from_numpy(vals), [L.AGG_SUM])[0].to_numpy()[0]
             assert gb.last_plan()["slots"] == pinned_slots("tile_boundaries_groupby_and_filter", n, env)
+            assert gb.last_plan() == pinned_plan("tile_boundaries_groupby_and_filter", n, env)
             assert np.array_equal(got.view(np.uint64), orc.groupby_agg(orc.AGG_SUM, ids, len(uniq), vals)[0].view(np.uint64))
         finally:
             os.environ.pop("PDX_HASH_PARTITION", None)

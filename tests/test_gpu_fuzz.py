@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from _create_plans import pinned_slots
+from _create_plans import pinned_plan, pinned_slots
 
 pytestmark = pytest.mark.gpu
 
@@ -93,6 +93,7 @@ def test_groupby_fuzz(px, monkeypatch, seed, mode):
     assert np.array_equal(np.ones(G, bool) if uok is None else uok, ~isnull) and np.array_equal(uk[~isnull], uniq[~isnull])
     outs = gb.agg(px.Column.from_numpy(vals, vvalid, offset=int(seed % 5)), kinds)
     assert gb.last_plan()["slots"] == pinned_slots("groupby_fuzz", seed, mode)
+    assert gb.last_plan() == pinned_plan("groupby_fuzz", seed, mode)
     for kind, out in zip(kinds, outs):
         got, ok = out.to_numpy()
         exp, eok = orc.groupby_agg(kind, ids, G, vals, vvalid, nthreads=4)
@@ -135,6 +136,7 @@ def test_groupby_fuzz_bound_columns(px, monkeypatch, seed, mode):
         check(k, gb.agg(vcol, [k])[0], "single")
         assert gb.last_plan()["bound"] == "1"
         assert gb.last_plan()["slots"] == pinned_slots("groupby_fuzz_bound_columns", seed, mode)
+        assert gb.last_plan() == pinned_plan("groupby_fuzz_bound_columns", seed, mode, k)
     for k, out in zip(kinds, gb.agg(vcol, kinds)):
         check(k, out, "together")
     for k in reversed(kinds):

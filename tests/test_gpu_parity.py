@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from _create_plans import pinned_slots
+from _create_plans import pinned_plan, pinned_slots
 from conftest import assert_f64_bits, golden
 
 pytestmark = pytest.mark.gpu
@@ -333,6 +333,7 @@ def test_groupby_golden(px, monkeypatch, name, hashmode):
         vcol = px.Column.from_numpy(c[keyname], vvalid, offset=2)
         outs = gb.agg(vcol, list(GB.values()))  # all five from one grouped pass
         assert gb.last_plan()["slots"] == pinned_slots("groupby_golden", name, hashmode)
+        assert gb.last_plan() == pinned_plan("groupby_golden", name, hashmode, col)
         for (k, kind), out in zip(GB.items(), outs):
             vals, ok = out.to_numpy()
             exp = c[f"{col}_{k}"]
@@ -401,6 +402,7 @@ def test_groupby_sizes_vs_oracle(px, monkeypatch, n, nk, dense):
     gb = px.K.GroupByHandle.create(px.Column.from_numpy(keys))
     s, m, cnt, lo, hi = gb.agg(px.Column.from_numpy(vals), [0, 1, 4, 2, 3])
     assert gb.last_plan()["slots"] == pinned_slots("groupby_sizes_vs_oracle", n, nk, dense, os.environ.get("PDX_HASH_PARTITION", "default"))
+    assert gb.last_plan() == pinned_plan("groupby_sizes_vs_oracle", n, nk, dense, os.environ.get("PDX_HASH_PARTITION", "default"))
     ek, es, em, ec = orc.groupby_sum_mean_count(keys, vals, nthreads=8)
     assert np.array_equal(gb.unique_keys().to_numpy()[0], ek)
     assert np.array_equal(cnt.to_numpy()[0], ec)
@@ -428,6 +430,7 @@ def test_groupby_skewed_vs_oracle(px, monkeypatch, n, nk, dtype, dense):
     ids, uniq, _, _ = orc.group_ids(keys)
     outs = gb.agg(px.Column.from_numpy(vals), [0, 1, 4, 2, 3])
     assert gb.last_plan()["slots"] == pinned_slots("groupby_skewed_vs_oracle", n, nk, dtype, dense)
+    assert gb.last_plan() == pinned_plan("groupby_skewed_vs_oracle", n, nk, dtype, dense)
     assert np.array_equal(gb.unique_keys().to_numpy()[0], uniq)
     for out, kind in zip(outs, (orc.AGG_SUM, orc.AGG_MEAN, orc.AGG_COUNT, orc.AGG_MIN, orc.AGG_MAX)):
         got = out.to_numpy()[0]
@@ -460,6 +463,7 @@ def test_groupby_dense_with_nulls_and_negative_keys(px, monkeypatch, dense):
     assert np.array_equal(gb.first_rows().cpu().numpy(), first)
     s = gb.agg(px.Column.from_numpy(vals), [0])[0].to_numpy()[0]
     assert gb.last_plan()["slots"] == pinned_slots("groupby_dense_with_nulls_and_negative_keys", dense, os.environ.get("PDX_HASH_PARTITION", "default"))
+    assert gb.last_plan() == pinned_plan("groupby_dense_with_nulls_and_negative_keys", dense, os.environ.get("PDX_HASH_PARTITION", "default"))
     assert_f64_bits(s, orc.groupby_agg(orc.AGG_SUM, ids, len(uniq), vals)[0])
 
 
@@ -620,6 +624,7 @@ def test_groupby_next_aggs_golden(px, monkeypatch, name, hashmode):
         vcol = px.Column.from_numpy(c[keyname], vvalid, offset=2)
         outs = gb.agg(vcol, [0] + list(GB_NEXT.values()))  # together with a standard kind in one call
         assert gb.last_plan()["slots"] == pinned_slots("groupby_next_aggs_golden", name, hashmode)
+        assert gb.last_plan() == pinned_plan("groupby_next_aggs_golden", name, hashmode, col)
         for (k, kind), out in zip(GB_NEXT.items(), outs[1:]):
             vals, ok = out.to_numpy()
             exp = c[f"{col}_{k}"]
@@ -688,6 +693,7 @@ def test_groupby_split_partition_special_keys(px, monkeypatch):
     assert np.array_equal(gb.first_rows().cpu().numpy(), first)
     s, c, mx = gb.agg(px.Column.from_numpy(vals, vvalid), [0, 4, 3])
     assert gb.last_plan()["slots"] == pinned_slots("groupby_split_partition_special_keys")
+    assert gb.last_plan() == pinned_plan("groupby_split_partition_special_keys")
     for out, kind in ((s, 0), (c, 4), (mx, 3)):
         got, ok = out.to_numpy()
         exp, eok = orc.groupby_agg(kind, ids, len(uniq), vals, vvalid, nthreads=8)
@@ -875,6 +881,7 @@ def test_groupby_hash_half_null_keys(px, monkeypatch, shape, head):
     assert np.array_equal(gb.first_rows().cpu().numpy(), first)
     s, c = gb.agg(px.Column.from_numpy(vals), [0, 4])
     assert gb.last_plan()["slots"] == pinned_slots("groupby_hash_half_null_keys", shape, head)
+    assert gb.last_plan() == pinned_plan("groupby_hash_half_null_keys", shape, head)
     for out, kind in ((s, 0), (c, 4)):
         got, ok = out.to_numpy()
         exp, eok = orc.groupby_agg(kind, ids, len(uniq), vals, None, nthreads=8)
